@@ -14,6 +14,12 @@ parallel cross-shard replay).  Inputs are synthetic (counter-based generator,
 identical on CPU and GPU) and resident in HBM before timing starts.
 --workload c1 / c2 run BASELINE configs[0] / [1] the same way.
 
+A plain run sets up, warms up, times --steps steps, writes the last step's
+results with --dump-outputs DIR and prints the result line.  --full adds the
+legs the headline figure does not need: the CPU baseline, the self-check of
+sampled result rows against the oracle, the committed PMC records next to the
+roofline, and with --sharded at one rank the comparison with the single index.
+
 Prints ONE JSON line on rank 0 (contract in the task statement).
 """
 from __future__ import annotations
@@ -61,6 +67,7 @@ ROUTE_KERNEL = {1: "k_qs_blockkey", 2: "k_qs_blockkey_w4", 3: "k_q8_blockkey", 4
 # at 4 cycles per wave64 (measured: k_bq_blockmin_lds sustains 33.6 T instr-lane-ops/s).
 VALU_PEAK_TOPS = 39.3
 HBM_PEAK_GBPS = 8000.0          # MI355X HBM3E (MI355X_MICROARCH.md)
+DUMP_MAX_BYTES = 64_000_000     # --dump-outputs writes at most this much
 GEMV_MAX = 8                   # runtime.hip default "gemv_max": batches up to 8 queries take k_gemv_select
 
 # BASELINE configs[3]: BQ 50M x 1536 over 8 GPUs -> one GPU holds a 6.25M-row shard
@@ -339,6 +346,31 @@ def measured_clock(workload: str, n_local: int, dims: int, batch: int, kernel: s
     return best
 
 
+def dump_outputs(path: str, res) -> None:
+    """--dump-outputs: what a caller of the timed path receives from the last
+    timed step -- ids [B, k] (float64: doc ids are exact below 2^53), dists
+    [B, k] (float32, as returned) and counts [B] (float64), every query of the
+    batch (c2, the largest: 10k x 100 -> 12 MB).  Slots past a query's count,
+    which the search does not write, are stored as id -1 / distance 0.  A
+    --batch so large that the arrays would pass 64 MB keeps a fixed seeded
+    sample of the queries, their indices in rows.npy."""
+    ids, dists, counts = (t.cpu().numpy() for t in res)
+    ids = ids.view(np.int64).astype(np.float64)
+    dists = dists.astype(np.float32)
+    unused = np.arange(ids.shape[1])[None, :] >= counts[:, None]
+    ids[unused] = -1.0
+    dists[unused] = 0.0
+    os.makedirs(path, exist_ok=True)
+    keep = DUMP_MAX_BYTES // (ids.shape[1] * 12 + 16)
+    if keep < ids.shape[0]:
+        rows = np.sort(np.random.default_rng(0).choice(ids.shape[0], keep, replace=False))
+        ids, dists, counts = ids[rows], dists[rows], counts[rows]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "ids.npy"), ids)
+    np.save(os.path.join(path, "dists.npy"), dists)
+    np.save(os.path.join(path, "counts.npy"), counts.astype(np.float64))
+
+
 def free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -390,11 +422,19 @@ def main():
                     help="corpus rows (--rows under torch.distributed.run: its parser claims --n as a prefix)")
     ap.add_argument("--dims", type=int, default=None,
                     help="exact flat workloads: override the row width (e.g. 1024 / 1536, the block-key w4 kernel)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the CPU baseline, "
+                         "the self-check of sampled result rows against the oracle, the committed PMC records of the "
+                         "roofline and (--sharded at one rank) the comparison with the single-index search")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (ids, dists, counts of every query of the batch) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--option", action="append", default=[],
                     help="index option key=value (wv_index_set_option), e.g. qs_w4=1; repeatable")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the self-check of sampled result rows against the oracle (outside the timed region)")
+                    help="--full: skip the self-check of sampled result rows against the oracle (outside the timed "
+                         "region)")
     ap.add_argument("--sharded", action="store_true",
                     help="run the multi-GPU path (the multi-shard index over RCCL, multi.hip) even at WORLD_SIZE 1 "
                          "(launch under torch.distributed.run): a one-GPU check of the N>1 path")
@@ -404,6 +444,8 @@ def main():
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per k_mfma_select launch from the rocprofv3 PMC pass")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     rc = maybe_relaunch(sys.argv[1:], args.gpus)
     if rc is not None:
         sys.exit(rc)
@@ -544,8 +586,10 @@ def main():
     route = int(index.stats().get("last_route", 0))
     if multi is not None:
         replays = multi.stats()["flagged"] - flagged0  # the cross-shard replay's queries (every rank's view)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res[:3])
     sharded_check = None
-    if args.sharded and world == 1:
+    if args.full and args.sharded and world == 1:
         # the sharded protocol at one rank must equal the single-index search
         si, sd, sn = (t.clone() for t in step()[:3])
         s = torch.cuda.current_stream(dev).cuda_stream
@@ -586,7 +630,7 @@ def main():
     dom_kernel = (pq_kernel if pq else ("k_q8_blockkey_bq" if route == 6 else "k_bq_blockmin_lds") if bq else
                   ("k_rq8_keys" if route == 10 else "k_rq8_dist" if rq_bits == 8 else "k_rq1_dist") if rq_bits
                   else sel_kernel)
-    if args.traffic_bytes is None:
+    if args.full and args.traffic_bytes is None:
         args.traffic_bytes = measured_traffic(args.workload, n_local, dims, B, dom_kernel)
     if rq_bits and route == 10:
         # dominant kernel: k_rq8_keys (rq8_mfma.hip), the
@@ -712,12 +756,12 @@ def main():
                 "traffic": args.traffic_bytes,
                 # DVFS: the chip holds a lower clock under this MFMA load; the PMC
                 # record gives the clock and the MFMA pipe's busy fraction
-                "pmc_clock": measured_clock(args.workload, n_local, dims, B, sel_kernel)}
+                "pmc_clock": measured_clock(args.workload, n_local, dims, B, sel_kernel) if args.full else None}
 
     result = None
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline:  # every world size: rank 0, outside the timed region
+        if args.full and not args.no_cpu_baseline:  # every world size: rank 0, outside the timed region
             try:
                 if rq_bits:
                     cpu = cpu_baseline_rq(rq_bits, min(args.cpu_rows, 200_000), args.cpu_queries or 512,
@@ -738,7 +782,7 @@ def main():
             except Exception as e:  # baseline failure must not hide the GPU number
                 log(f"cpu baseline failed: {e}")
         check = None
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             try:
                 check = verify_sample(args.workload, flat, gen_kind, n_total, dims, B, K_, res[:3], index,
                                       args.cpu_threads, BQ_RESCORE, world)

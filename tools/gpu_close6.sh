@@ -2,7 +2,7 @@
 # closing check on the final tree: C3 bench line, serving at the library's default window
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/${1:-close6}; mkdir -p $O
-timeout -k 10 420 python -u bench.py > $O/bench_c3.json 2> $O/bench_c3.err || { tail -5 $O/bench_c3.err; exit 1; }
+timeout -k 10 420 python -u bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err || { tail -5 $O/bench_c3.err; exit 1; }
 tail -c 400 $O/bench_c3.json
 timeout -k 10 150 tools/serve_bench 10000000 256 8 > $O/serve_c3_256.json 2> $O/serve_c3_256.err || { tail $O/serve_c3_256.err; exit 1; }
 cat $O/serve_c3_256.json

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/${1:-final6}; mkdir -p $O
 run() {  # name, bench args
     local n=$1; shift
-    timeout -k 10 420 python -u bench.py "$@" > $O/bench_$n.json 2> $O/bench_$n.err; local rc=$?
+    timeout -k 10 420 python -u bench.py --full "$@" > $O/bench_$n.json 2> $O/bench_$n.err; local rc=$?
     echo "$n rc=$rc"; tail -c 600 $O/bench_$n.json
     [ $rc -eq 0 ] || { tail -5 $O/bench_$n.err; exit $rc; }
 }
