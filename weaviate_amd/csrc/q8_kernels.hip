@@ -324,6 +324,31 @@ struct Q8Args {
 };
 namespace {
 
+// k_q8_blockkey<.., SEAM>: the chunks of a slot (2 NC chunks, PF = 1) that
+// carry the previous slot's deferred second-block reduction (RD), its combine
+// and key store (KS), and the slot's barrier (XB); the P0 vector-memory ops of
+// group t+2 go at chunks XB+1 .. XB+P0.  XB = NC, block 1's first chunk, is
+// the measured optimum at NC = 12 (C3: key pass vs the in-order loop +0.6 % at
+// XB = 3, -0.4 % at 5, -1.6 % at 8, -2.1 % at 10, -1.9 % at 11, -2.2 .. -2.9 %
+// at 12, -0.5 % at 14; a second barrier per slot -- an early one that frees
+// slot t-1 for a two-slot DMA lead, a late one for the landing -- +8.1 %).
+constexpr int Q8_SEAM_RD = 1, Q8_SEAM_KS = 2;
+constexpr int q8_seam_xb(int nc) { return nc; }
+constexpr bool q8_seam_fits(int nc, bool l2) {
+    const int xb = q8_seam_xb(nc);
+    const int p0 = nc / 2 + 2 + (l2 ? 1 : 0);  // pieces + valid words + scales (+ L2 norms)
+    // the barrier follows every read of the previous slot (XB >= PF = 1) and the
+    // key store (KS <= XB: the store is the one op younger than group t+1 at the
+    // wait); the group ends inside the slot; the deferred reduction reads acc[1]
+    // before block 1's first MFMA (chunk NC) and the combine reads block 0's
+    // partials before they are rewritten (chunk NC + 1)
+    return xb >= 1 && xb + p0 < 2 * nc && Q8_SEAM_RD < Q8_SEAM_KS && Q8_SEAM_KS <= xb && Q8_SEAM_RD < nc &&
+           Q8_SEAM_KS < nc + 1;
+}
+static_assert(q8_seam_fits(8, false) && q8_seam_fits(8, true) && q8_seam_fits(10, false) && q8_seam_fits(10, true) &&
+                  q8_seam_fits(12, false) && q8_seam_fits(12, true),
+              "SEAM chunk placement");
+
 // ---------------------------------------------------------------------------
 // k_q8_blockkey<NC, RB, L2>: block keys of 256 queries (8 waves x 32) x one
 // span of the corpus, NC 64-column chunks per 32-row block, RB blocks per LDS
@@ -335,7 +360,9 @@ namespace {
 // halves x 2 query halves), one DMA piece of the group two steps ahead.  The
 // reduction over a block's rows runs beside the next block's MFMAs (RB = 2)
 // or after the slot; the cross-lane combine + key store of a slot's last
-// block is deferred into the next slot.  One barrier per slot.
+// block is deferred into the next slot.  One barrier per slot.  (The paired
+// variants run the SEAM schedule below by default: the barrier mid-slot, the
+// DMA one step ahead, the second block's reduction deferred as well.)
 // ---------------------------------------------------------------------------
 // STAG (RB = 2): waves 4-7 -- each the SIMD partner of wave w - 4 -- run every
 // block's reduction P0 chunks into the next block instead of right after it
@@ -376,8 +403,30 @@ namespace {
 // wave's vector-memory counts, which the ring's vmcnt waits rely on, are those
 // of the full schedule.  A batch of 64 queries runs the MFMAs of 2 waves
 // instead of 8 (the HBM stream of the plane is then the bound).
+// SEAM (PAIR, PF = 1; option q8_sched = 1, the default; 0 = the in-order slot
+// loop): the seamless ring.  The in-order schedule ends every slot with a tail
+// that all 8 waves run together -- the second block's reduction behind the
+// slot's last MFMA, the vmcnt wait, the barrier, then the next slot's first
+// fragment reads with their LDS latency exposed.  SEAM has no slot boundary
+// (C3: the key pass 2-3 % shorter; the barrier itself, not its
+// tail, is the larger cost -- a second one per slot adds 8 %):
+//   - the slot's one barrier sits at chunk XB, after that chunk's MFMAs.  The
+//     wave first waits (counted vmcnt) for its own pieces of group t+1, so the
+//     barrier certifies that group t+1 has landed for every wave (first read:
+//     chunk NT - 1) and that every wave's reads of slot t-1 have retired (the
+//     lgkmcnt wait of chunk 0 at the latest).  No fragment read depends on it:
+//     the registers in flight belong to slot t, and MFMA issue goes on;
+//   - group t+2's DMA pieces follow that barrier (chunks XB+1 .. XB+P0) into
+//     slot t-1's buffer: the ring runs one slot ahead instead of two;
+//   - the ordinary one-chunk-ahead fragment read of the last chunk wraps into
+//     the next slot's buffer, so the lgkmcnt counts are the same at every chunk;
+//   - the second block's reduction is deferred to chunk RD of the next slot,
+//     beside block 0's MFMAs (acc[1] is rewritten from chunk NC on), its
+//     combine and key store to chunk KS; the slot's second valid word, scale
+//     and L2 norms are carried across the iteration.
+// The same MFMAs, fragments, DMA pieces and keys as the in-order schedule.
 template <int NC, int RB, bool ISL2, bool STAG = false, bool BQ = false, int PF = 1, int DBG = 0, bool LIVE = false,
-          bool MASK = false>
+          bool MASK = false, bool SEAM = false>
 __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
     constexpr int NPB = 2 * NC;                     // 1 KiB pieces per 32-row block
     constexpr int SLOT = RB * NPB * 1024;           // bytes per ring slot
@@ -393,6 +442,9 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
     static_assert(!BQ || (!ISL2 && !STAG), "BQ: integer maxima, in-order schedule");
     static_assert(!LIVE || (RB == 2 && !STAG && !BQ && DBG == 0), "LIVE: the paired in-order schedule");
     static_assert(!MASK || (RB == 2 && !STAG && !BQ && !ISL2 && DBG == 0), "MASK: paired dot / cosine keys");
+    static_assert(!SEAM || (RB == 2 && !STAG && !BQ && !MASK && PF == 1), "SEAM: the paired in-order variants, PF = 1");
+    static_assert(!SEAM || q8_seam_fits(NC, ISL2), "SEAM: group t+2 is issued between the barrier and the slot's end");
+    constexpr int XB = q8_seam_xb(NC), RD = Q8_SEAM_RD, KS = Q8_SEAM_KS;
     constexpr int X0 = 1;                           // chunk of the slot's extra LDS reads
     constexpr int XE = 2 + (ISL2 ? 2 * RB : 0) + (MASK ? 2 : 0);  // extra reads: valid words, scales (+ norms / masks)
     constexpr int NBUF = 3;
@@ -695,6 +747,153 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
     // static priority for the younger half of the SIMD pairs (MI355X_MICROARCH.md,
     // two waves per SIMD, item 4): one s_setprio before the loop, none inside
     if (a.prio && wave >= 4) __builtin_amdgcn_s_setprio(1);
+    // SEAM: the previous slot's second block until its deferred reduction (its
+    // accumulators stay in acc[1]): valid word, L2 norms; its scale is psB
+    uint32_t cvw = 0;
+    f32x4_t cxa = {0.f, 0.f, 0.f, 0.f}, cxb = {0.f, 0.f, 0.f, 0.f};
+    // ---------------------------------------------------------------------
+    // The SEAM slot loop.  A wave's vector-memory ops in issue order (G(j) =
+    // the P0 ops of group j, S(j) = the key store of slot j), with the wait W(t)
+    // of slot t's barrier:
+    //   prologue   G(0) G(1)            vmcnt(P0), barrier: group 0 has landed
+    //   slot 0     W(0) G(2)            W(0): G(1) is the youngest op -> vmcnt(0)
+    //   slot 1     S(0) W(1) G(3)       W(1): G(2), then S(0)         -> vmcnt(1)
+    //   slot t     S(t-1) W(t) G(t+2)   W(t): G(t+1), then S(t-1)     -> vmcnt(1)
+    //   slot n-2   S(n-3) W(n-2)        W(n-2): G(n-1), then S(n-3)   -> vmcnt(1)
+    //   slot n-1   S(n-2)               no barrier: nothing is read past the slot
+    //   epilogue   S(n-1)
+    // (n = nsteps; a span of one slot runs neither wait nor barrier, a span of two
+    // W(0) only; G(t+2) is absent from the last two slots.)  So W(t) lets exactly
+    // the ops younger than group t+1's last piece stay in flight -- no store
+    // retirement is waited on -- and group t+1, whose first read is chunk NT - 1
+    // of slot t, has landed for every wave behind slot t's barrier.  G(t+2)
+    // overwrites the buffer of slot t-1 and entry (t+2) & 3 of the wave's own
+    // valid / scale / norm rings: every wave's last read of slot t-1 (issued at
+    // its chunk NT - 2) retired at the lgkmcnt wait of its chunk NT - 1, before
+    // that wave reached slot t's barrier, and ring entry (t-2) & 3 was read in
+    // slot t-2.  Every wave executes the same barriers and vector-memory ops
+    // (LIVE's ACT = false copy included): nsteps is uniform over the workgroup.
+    // A wrong count here is a silent LDS race, not a fault.
+    // ---------------------------------------------------------------------
+    auto seam_loop = [&](auto actc) {
+    constexpr bool ACT = decltype(actc)::value;
+    static_assert(NT % NB2 == 0, "the fragment sets continue across the slot boundary");
+    int cur = 0;
+    for (int t = 0; t < nsteps; t++) {
+        const int nxt = cur == NBUF - 1 ? 0 : cur + 1;
+        const int gslot = cur == 0 ? NBUF - 1 : cur - 1;  // slot of group t+2 (= of slot t-1)
+        const unsigned sbase = ring + (unsigned)(cur * SLOT) + l16;
+        const unsigned snext = ring + (unsigned)(nxt * SLOT) + l16;
+        // uniform: scalar branches
+        const int more = __builtin_amdgcn_readfirstlane(t + 1 < nsteps ? 1 : 0);
+        const int dma = __builtin_amdgcn_readfirstlane(t + 2 < nsteps ? 1 : 0);
+        const unsigned sm = (unsigned)(t & 3);
+        uint2 vwv = uint2{0u, 0u};
+        float2 sbv = float2{0.f, 0.f};
+        f32x4_t xa[RB], xb[RB];
+#pragma unroll
+        for (int r = 0; r < RB; r++) xa[r] = xb[r] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        static_for<0, NT>([&](auto ttc) {
+            constexpr int tt = decltype(ttc)::value;
+            constexpr int rb = tt / NC, c = tt % NC;
+            if constexpr (tt == X0 && ACT) {  // this slot's valid words, scales (+ L2 norms)
+                asm volatile("ds_read_b64 %0, %1" : "=v"(vwv) : "v"(vring + sm * 16u));
+                asm volatile("ds_read_b64 %0, %1" : "=v"(sbv) : "v"(sring + sm * 16u));
+                if constexpr (ISL2) {
+                    const unsigned xbase = xnring + sm * (unsigned)(RB * 128) + (unsigned)(16 * ((lane >> 4) & 3));
+                    xa[0] = lds_ld4f_o<0>(xbase);
+                    xb[0] = lds_ld4f_o<64>(xbase);
+                    xa[1] = lds_ld4f_o<128>(xbase);
+                    xb[1] = lds_ld4f_o<192>(xbase);
+                }
+            }
+            // the fragments one chunk ahead; the last chunk's are the next slot's
+            // first (group t+1: behind this slot's barrier)
+            if constexpr (tt + 1 < NT) {
+                if constexpr (ACT) {
+                    constexpr int o1 = ((tt + 1) / NC * NPB + 2 * ((tt + 1) % NC)) * 1024;
+                    B2[(tt + 1) % NB2][0] = lds_ld16_o<o1>(sbase);
+                    B2[(tt + 1) % NB2][1] = lds_ld16_o<o1 + 512>(sbase);
+                }
+                qs_wait_lgkm<2 + (tt == X0 ? XE : 0)>();
+            } else {
+                if (more) {
+                    if constexpr (ACT) {
+                        B2[0][0] = lds_ld16_o<0>(snext);
+                        B2[0][1] = lds_ld16_o<512>(snext);
+                    }
+                    qs_wait_lgkm<2>();
+                } else {
+                    qs_wait_lgkm<0>();
+                }
+            }
+            asm volatile("" : "+v"(B2[tt % NB2][0]), "+v"(B2[tt % NB2][1]));
+            if constexpr (tt == X0 + 1 && ACT) {
+                if constexpr (ISL2) asm volatile("" : "+v"(vwv), "+v"(sbv), "+v"(xa[0]), "+v"(xb[0]), "+v"(xa[1]), "+v"(xb[1]));
+                else asm volatile("" : "+v"(vwv), "+v"(sbv));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (ACT)
+#pragma unroll
+            for (int m = 0; m < 2; m++)
+#pragma unroll
+                for (int n = 0; n < 2; n++) {
+                    if constexpr (DBG & 2) { acc[rb][m][n] = B2[tt % NB2][m]; continue; }
+                    if constexpr (c == 0)
+                        acc[rb][m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(B2[tt % NB2][m], Qf[2 * c + n],
+                                                                              i32x4_t{0, 0, 0, 0}, 0, 0, 0);
+                    else
+                        acc[rb][m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(B2[tt % NB2][m], Qf[2 * c + n],
+                                                                              acc[rb][m][n], 0, 0, 0);
+                }
+            // the previous slot's second block: its reduction from acc[1] ...
+            if constexpr (tt == RD && !(DBG & 4) && ACT) {
+                if (t > 0) reduce_raw(acc[1], cvw, psB, cxa, cxb, pB0, pB1);
+            }
+            // ... and the slot's cross-lane combine + key store
+            if constexpr (tt == KS && !(DBG & 4)) {
+                if (t > 0) finish2(pA0, pA1, pB0, pB1, psA, psB, gbp);
+            }
+            // the barrier: W(t), see above
+            if constexpr (tt == XB) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (more) {
+                    if constexpr (DBG != 0) {
+                        qs_wait_vm_c<0>();
+                    } else if (t > 0) {
+                        qs_wait_vm_c<1>();
+                    } else {
+                        qs_wait_vm_c<0>();
+                    }
+                    __builtin_amdgcn_s_barrier();  // group t+1 has landed, slot t-1 is free, for every wave
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // DMA of group t+2: one piece per chunk
+            if constexpr (tt > XB && tt <= XB + P0) {
+                if (dma) issue_piece(tt - XB - 1, t + 2, gslot);
+            }
+            // block 0's partials beside block 1's MFMAs
+            if constexpr (tt == NC + 1 && !(DBG & 4) && ACT) reduce_raw(acc[0], vwv.x, sbv.x, xa[0], xb[0], pA0, pA1);
+        });
+        if constexpr (ACT) {
+            psA = sbv.x;
+            psB = sbv.y;
+            cvw = vwv.y;
+            if constexpr (ISL2) {
+                cxa = xa[1];
+                cxb = xb[1];
+            }
+            if constexpr ((DBG & 4) != 0) {
+#pragma unroll
+                for (int r = 0; r < RB; r++)
+                    dbg_sink ^= acc[r][0][0][0] ^ acc[r][0][1][0] ^ acc[r][1][0][0] ^ acc[r][1][1][0];
+            }
+        }
+        gbp = (s0 + t) * RB;
+        cur = nxt;
+    }
+    };
     // the slot loop; LIVE: a second copy for a wave without queries (ACT false:
     // no fragment reads, MFMAs or reductions; the same DMA, key stores and
     // barriers), so neither copy branches around its MFMAs
@@ -842,14 +1041,22 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
         cur = nxt;
     }
     };
-    if constexpr (LIVE) {
+    if constexpr (SEAM && LIVE) {
+        if (act) seam_loop(std::true_type{});
+        else seam_loop(std::false_type{});
+    } else if constexpr (SEAM) {
+        seam_loop(std::true_type{});
+    } else if constexpr (LIVE) {
         if (act) slot_loop(std::true_type{});
         else slot_loop(std::false_type{});
     } else {
         slot_loop(std::true_type{});
     }
     if (nsteps > 0 && !(DBG & 4)) {
-        if constexpr (PAIR) {
+        if constexpr (SEAM) {  // the last slot's second block was not reduced in the loop
+            if (act) reduce_raw(acc[1], cvw, psB, cxa, cxb, pB0, pB1);
+            finish2(pA0, pA1, pB0, pB1, psA, psB, gbp);
+        } else if constexpr (PAIR) {
             finish2(pA0, pA1, pB0, pB1, psA, psB, gbp);
         } else {
             if (late) reduce(acc[RB - 1], dvw, dsb, dxa, dxb, mp0, mp1);

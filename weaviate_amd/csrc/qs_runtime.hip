@@ -61,17 +61,26 @@ int launch_q8_keys(wv_index* idx, hipStream_t s, Q8Args a, int dpb8, bool l2) {
     a.nspans = (int)((a.nslots + sps - 1) / sps);
     const size_t lds = (size_t)3 * RB * 2 * NC8 * 1024 + 1024 + (l2 ? (size_t)8 * 4 * RB * 128 : 0);
     dim3 grid((unsigned)((int64_t)a.nqg * a.nspans));
+    const bool seam = idx->q8_sched && !idx->q8_stag && idx->q8_pf == 1;
 #define WV_Q8K(NCV, RBV, L2V)                                                                                  \
     do {                                                                                                       \
         HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<NCV, RBV, L2V, false, false, 1>,                 \
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                     \
         k_q8_blockkey<NCV, RBV, L2V, false, false, 1><<<grid, 512, lds, s>>>(a);                                \
     } while (0)
+// the paired kernel (two blocks per slot): the seamless ring unless q8_sched = 0, q8_stag or q8_pf = 2
+#define WV_Q8KP(NCV, L2V)                                                                                      \
+    do {                                                                                                       \
+        if (!seam) { WV_Q8K(NCV, 2, L2V); break; }                                                             \
+        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<NCV, 2, L2V, false, false, 1, 0, false, false, true>, \
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                     \
+        k_q8_blockkey<NCV, 2, L2V, false, false, 1, 0, false, false, true><<<grid, 512, lds, s>>>(a);          \
+    } while (0)
 #define WV_Q8KN(L2V)                                   \
     switch (NC8) {                                     \
-    case 8: WV_Q8K(8, 2, L2V); break;                  \
-    case 10: WV_Q8K(10, 2, L2V); break;                \
-    case 12: WV_Q8K(12, 2, L2V); break;                \
+    case 8: WV_Q8KP(8, L2V); break;                    \
+    case 10: WV_Q8KP(10, L2V); break;                  \
+    case 12: WV_Q8KP(12, L2V); break;                  \
     case 16: WV_Q8K(16, 1, L2V); break;                \
     case 20: WV_Q8K(20, 1, L2V); break;                \
     case 24: WV_Q8K(24, 1, L2V); break;                \
@@ -79,6 +88,7 @@ int launch_q8_keys(wv_index* idx, hipStream_t s, Q8Args a, int dpb8, bool l2) {
     }
     if (l2) { WV_Q8KN(true); } else { WV_Q8KN(false); }
 #undef WV_Q8KN
+#undef WV_Q8KP
 #undef WV_Q8K
     HIPCHK(hipGetLastError());
     return WV_OK;
@@ -282,9 +292,21 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
         k_q8_blockkey<NCV, RBV, L2V, STV, false, PFV><<<grid, 512, lds, s>>>(q8a);                              \
     } while (0)
 #define WV_Q8(NCV, RBV, L2V) do { if (idx->q8_pf == 2) WV_Q8S(NCV, RBV, L2V, false, 2); else WV_Q8S(NCV, RBV, L2V, false, 1); } while (0)
+// the paired kernel on the seamless ring (option q8_sched; q8_stag and q8_pf = 2 keep the in-order slot loop)
+#define WV_Q8E(NCV, L2V, LIVEV)                                                                                \
+    do {                                                                                                       \
+        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<NCV, 2, L2V, false, false, 1, 0, LIVEV, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        k_q8_blockkey<NCV, 2, L2V, false, false, 1, 0, LIVEV, false, true><<<grid, 512, lds, s>>>(q8a);        \
+    } while (0)
+        const bool q8seam = idx->q8_sched && !idx->q8_stag && idx->q8_pf == 1;
 #ifdef WV_QS_DBG  // timing experiments (k_q8_blockkey DBG bits), not in the product build
 #define WV_Q8D(DV)                                                                                             \
     do {                                                                                                       \
+        if (q8seam) {                                                                                          \
+            HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<12, 2, false, false, false, 1, DV, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            k_q8_blockkey<12, 2, false, false, false, 1, DV, false, false, true><<<grid, 512, lds, s>>>(q8a);  \
+            break;                                                                                             \
+        }                                                                                                      \
         HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<12, 2, false, false, false, 1, DV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
         k_q8_blockkey<12, 2, false, false, false, 1, DV><<<grid, 512, lds, s>>>(q8a);                           \
     } while (0)
@@ -308,7 +330,10 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
         if constexpr (!L2V) {                                                                                  \
             if (pqk) { if (q8live) WV_Q8M(NCV, true); else WV_Q8M(NCV, false); break; }                       \
         }                                                                                                      \
-        if (idx->q8_stag) WV_Q8S(NCV, 2, L2V, true, 1); else if (q8live) WV_Q8L(NCV, L2V); else WV_Q8(NCV, 2, L2V); \
+        if (idx->q8_stag) WV_Q8S(NCV, 2, L2V, true, 1);                                                        \
+        else if (q8seam) { if (q8live) WV_Q8E(NCV, L2V, true); else WV_Q8E(NCV, L2V, false); }                 \
+        else if (q8live) WV_Q8L(NCV, L2V);                                                                     \
+        else WV_Q8(NCV, 2, L2V);                                                                               \
     } while (0)
 #define WV_Q8N(L2V)                                    \
     switch (NC8) {                                     \
@@ -342,7 +367,8 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
                 q8a.qmask_n = cn;
             }
 #ifdef WV_QS_DBG
-            if (idx->sel_dbg > 0 && !l2 && NC8 == 12) {
+            const bool q8dbg = idx->sel_dbg > 0 && !l2 && NC8 == 12;
+            if (q8dbg) {
                 switch (idx->sel_dbg) {
                 case 1: WV_Q8D(1); break;
                 case 2: WV_Q8D(2); break;
@@ -354,13 +380,16 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
                 case 9: WV_Q8D(9); break;
                 default: WV_Q8D(7); break;
                 }
-            } else
+            }
+#else
+            const bool q8dbg = false;
 #endif
             // small batches: the register-streaming kernel (one plane pass, no
             // 256-query padding of the MFMA work), the same keys
             const int qg = cn <= 16 ? 1 : 2;
             const bool gemv = idx->q8_gemv && !q8cp && !pqk && cn <= 32 && NC8 <= (qg == 1 ? 24 : 16) && nb < (1ll << 40);
-            if (gemv) {
+            if (q8dbg) {  // the timing build's launch above
+            } else if (gemv) {
                 idx->stats.last_route = WV_ROUTE_Q8_GEMV;
                 const unsigned gg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (nb + 3) / 4));
 #define WV_Q8G(NCV, QGV, L2V) k_q8_gemv<NCV, QGV, L2V><<<gg, 256, 0, s>>>(q8a, nb)
@@ -446,6 +475,7 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
 #undef WV_Q8M
 #undef WV_Q8L
 #undef WV_Q8S
+#undef WV_Q8E
 #undef WV_Q8
         HIPCHK(hipGetLastError());
         if (time_it) { HIPCHK(hipEventRecord(idx->ev1, s)); idx->timed = 1; }

@@ -154,6 +154,7 @@ struct wv_index {
     int q8_shape = 16;              // option q8_shape: 16 = v_mfma_i32_16x16x64_i8 kernel, 32 = 32x32x32
     int q8_stag = 0;
     int q8_pf = 1;                  // option q8_pf: A-fragment reads 1 or 2 chunks ahead                // option q8_stag: waves 4-7 reduce each block P0 chunks late (RB = 2)
+    int q8_sched = 1;               // option q8_sched: the paired int8 key kernel's slot loop: 1 = seamless ring (SEAM), 0 = in-order
     int q8_gemv = 1;                // option q8_gemv: batches of <= 32 queries stream the int8 plane through registers (k_q8_gemv)
     int q8_live = 1;                // option q8_live: waves of a partial query group's padding skip their MFMAs (k_q8_blockkey LIVE)
     int q8_prio = 0;                // option q8_prio: s_setprio 1 for waves 4-7 of k_q8_blockkey (experiment)
