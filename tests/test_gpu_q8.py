@@ -143,32 +143,6 @@ def test_q8_row_filter_equals_bf16_filter_and_unfiltered(wv, oracle, metric, var
 
 
 @pytest.mark.parametrize("metric,kind,d,k", [("cosine", 0, 768, 10), ("l2-squared", 1, 512, 100), ("dot", 0, 640, 10)])
-@pytest.mark.parametrize("variant_opt", [{"q8_stag": 1}, {"q8_pf": 2}])
-def test_q8_staggered_epilogue_same_keys(wv, oracle, metric, kind, d, k, variant_opt):
-    """q8_stag 1 (waves 4-7 reduce each block late) and q8_pf 2 (fragment reads
-    two chunks ahead) write the same block keys as the default schedule:
-    identical results and block keys, both equal to the oracle; corpus sizes
-    that end mid-slot and mid-span."""
-    n = 20000 + 37
-    data = gen(oracle, kind, 81, n, d)
-    queries = gen(oracle, kind, 82, 300, d)
-    res, keys = [], []
-    for opt in ({}, variant_opt):
-        idx, orc = build_pair(wv, oracle, metric, "avx256", data, options=opt)
-        res.append(idx.search_by_vector_batch(queries, k))
-        assert idx.stats()["last_route"] == ROUTE_INT8
-        keys.append([idx.debug_blockkeys(q)[0] for q in (0, 255, 299)])
-        idx.close()
-    for a, b in zip(res[0], res[1]):
-        np.testing.assert_array_equal(np.asarray(a).view(np.uint8), np.asarray(b).view(np.uint8))
-    for a, b in zip(keys[0], keys[1]):
-        np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
-    ids, dists, counts = res[1]
-    for qi in range(0, len(queries), 10):
-        assert_same(orc.search(queries[qi], k), ids[qi, :counts[qi]], dists[qi, :counts[qi]], f"{metric} q{qi}")
-
-
-@pytest.mark.parametrize("metric,kind,d,k", [("cosine", 0, 768, 10), ("l2-squared", 1, 512, 100), ("dot", 0, 640, 10)])
 @pytest.mark.parametrize("nq", [40, 64, 100, 300])
 def test_q8_live_padding_waves_same_keys(wv, oracle, metric, kind, d, k, nq):
     """q8_live (default 1): in a batch that is not a multiple of 256 queries the
@@ -195,13 +169,19 @@ def test_q8_live_padding_waves_same_keys(wv, oracle, metric, kind, d, k, nq):
 
 
 def test_q8_prio_same_keys(wv, oracle):
-    """q8_prio 1 (waves 4-7 at s_setprio 1) changes the issue order only."""
+    """q8_prio 1 (waves 4-7 at s_setprio 1) changes the issue order only.  The
+    retired schedule options (the stagger, prefetch distance 2) are refused as
+    unknown options."""
     n, d, k = 20000 + 37, 768, 10
     data = gen(oracle, 0, 85, n, d)
     queries = gen(oracle, 0, 86, 512, d)
     res = []
     for opt in ({"q8_prio": 0}, {"q8_prio": 1}):
         idx, orc = build_pair(wv, oracle, "cosine", "avx256", data, options=opt)
+        for key, value in (("q8_stag", 1), ("q8_pf", 2)):
+            with pytest.raises(wv.WeaviateError, match="unknown option") as err:
+                idx.set_option(key, value)
+            assert err.value.code == -1  # WV_ERR_INVALID
         res.append(idx.search_by_vector_batch(queries, k) + (idx.debug_blockkeys(300)[0],))
         idx.close()
     for a, b in zip(res[0], res[1]):

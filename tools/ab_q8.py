@@ -79,7 +79,7 @@ for B in (int(b) for b in args.batches.split(",")):
             key[i].append(float(np.median(ks)))
             out[i] = (oi[:B].cpu().clone(), od[:B].cpu().clone(), on[:B].cpu().clone())
             for kk in opts:  # back to the defaults for the next set
-                idx.set_option(kk, {"q8_live": 1, "q8_prio": 0, "q8_sched": 1, "q8_pf": 1}.get(kk, 0))
+                idx.set_option(kk, {"q8_live": 1, "q8_prio": 0, "q8_sched": 1}.get(kk, 0))
     same = all(all(bool(torch.equal(out[0][j], out[i][j])) for j in range(3)) for i in out)
     for i, opts in enumerate(sets):
         print(json.dumps({"B": B, "opts": opts, "ms": round(float(np.median(wall[i])), 4),

@@ -324,8 +324,21 @@ struct Q8Args {
 };
 namespace {
 
-// k_q8_blockkey<.., SEAM>: the chunks of a slot (2 NC chunks, PF = 1) that
-// carry the previous slot's deferred second-block reduction (RD), its combine
+// k_q8_blockkey's dynamic LDS: Q8_NBUF ring slots of RB blocks x 2 NC 1 KiB
+// pieces, then the per-wave rings of 4 entries: valid words and block scales
+// ([8 waves][4][16 B] each), then the L2 norms ([8][4][RB * 128 B]) or the MASK
+// words ([8][4][64 words]); L2 and MASK never occur together.  The kernel's
+// ring offsets and the launcher's byte count both come from these.
+constexpr int Q8_NBUF = 3;
+constexpr unsigned Q8_VS_RING = 8 * 4 * 16;   // bytes of the valid ring, and of the scale ring
+constexpr unsigned Q8_MASK_WAVE = 4 * 64 * 4;  // bytes of a wave's MASK ring
+constexpr unsigned q8_norm_wave(int rb) { return (unsigned)(4 * rb * 128); }  // bytes of a wave's L2 norm ring
+constexpr size_t q8_key_lds(int nc, int rb, bool l2, bool mask) {
+    return (size_t)Q8_NBUF * rb * 2 * nc * 1024 + 2 * Q8_VS_RING + (l2 ? 8 * q8_norm_wave(rb) : 0) +
+           (mask ? 8 * Q8_MASK_WAVE : 0);
+}
+
+// k_q8_blockkey<.., SEAM>: the chunks of a slot (2 NC chunks) that carry the previous slot's deferred second-block reduction (RD), its combine
 // and key store (KS), and the slot's barrier (XB); the P0 vector-memory ops of
 // group t+2 go at chunks XB+1 .. XB+P0.  XB = NC, block 1's first chunk, is
 // the measured optimum at NC = 12 (C3: key pass vs the in-order loop +0.6 % at
@@ -337,7 +350,7 @@ constexpr int q8_seam_xb(int nc) { return nc; }
 constexpr bool q8_seam_fits(int nc, bool l2) {
     const int xb = q8_seam_xb(nc);
     const int p0 = nc / 2 + 2 + (l2 ? 1 : 0);  // pieces + valid words + scales (+ L2 norms)
-    // the barrier follows every read of the previous slot (XB >= PF = 1) and the
+    // the barrier follows every read of the previous slot (XB >= 1) and the
     // key store (KS <= XB: the store is the one op younger than group t+1 at the
     // wait); the group ends inside the slot; the deferred reduction reads acc[1]
     // before block 1's first MFMA (chunk NC) and the combine reads block 0's
@@ -360,14 +373,15 @@ static_assert(q8_seam_fits(8, false) && q8_seam_fits(8, true) && q8_seam_fits(10
 // halves x 2 query halves), one DMA piece of the group two steps ahead.  The
 // reduction over a block's rows runs beside the next block's MFMAs (RB = 2)
 // or after the slot; the cross-lane combine + key store of a slot's last
-// block is deferred into the next slot.  One barrier per slot.  (The paired
-// variants run the SEAM schedule below by default: the barrier mid-slot, the
-// DMA one step ahead, the second block's reduction deferred as well.)
+// block is deferred into the next slot.  One barrier per slot.  A-fragment
+// reads run one chunk ahead of their MFMAs (two register sets).
 // ---------------------------------------------------------------------------
-// STAG (RB = 2): waves 4-7 -- each the SIMD partner of wave w - 4 -- run every
-// block's reduction P0 chunks into the next block instead of right after it
-// (MI355X_MICROARCH.md, two waves per SIMD, item 9: a stagger), so the two
-// waves of a SIMD do not issue their epilogue VALU at the same time.
+// RB = 1 (1024 .. 1536 columns): the in-order slot loop, one block per slot,
+// the unpaired reduce / finish.  RB = 2 (512 .. 768 columns): PAIR, on the
+// in-order slot loop or, by default, the SEAM ring; LIVE and MASK are paired
+// variants.  BQ runs the in-order loop at either RB.  A stagger of the SIMD
+// partners' epilogues and a fragment prefetch distance of 2 were measured
+// slower and removed.
 //
 // BQ (bq_kernels.hip's block minima on the matrix cores): X8 / Q8 are the
 // codes unpacked to +-1 (bit 0 -> +1, bit 1 -> -1; columns past the code bits
@@ -375,17 +389,16 @@ static_assert(q8_seam_fits(8, false) && q8_seam_fits(8, true) && q8_seam_fits(10
 // the minimum hamming distance of every 32-row block (+inf without a valid
 // row) -- 8x finer than the VALU kernels' 256-row minima, so the replay
 // (k_bq_replay<.., 32>) recomputes 8x fewer rows per visited block.
-// PF: A-fragment reads PF chunks ahead of their MFMAs (PF + 1 register sets).
-// PAIR (RB = 2, in-order schedule): a slot's two blocks share one cross-lane
-// combine and one 64-lane key store.  Each block's reduction leaves, per lane,
+// PAIR (RB = 2): a slot's two blocks share one cross-lane combine and one
+// 64-lane key store.  Each block's reduction leaves, per lane,
 // the partial of its row group for both query halves -- raw int32 maxima for
 // dot/cos/BQ (the positive scale commutes with the maximum, so it is applied
 // once after the combine), fl(xnorm2 - 2S) minima for L2 -- and the combine is
 // a transpose-reduction: permlane32 swaps pair (A half 0, A half 1) and (B half
 // 0, B half 1), one permlane16 swap pairs the two results, three max/min ops
 // in all, ending with lane group G = lane >> 4 holding block A / B (G & 1) of
-// query half G >> 1.  The unpaired form takes five swaps and four ops per
-// block and stores from 32 lanes.
+// query half G >> 1.  The unpaired form (RB = 1) takes five swaps and four
+// ops per block and stores from 32 lanes.
 // DBG (timing experiments in a -DWV_QS_DBG build only, wrong results): bit 0
 // drops the plane DMA, bit 1 the MFMAs, bit 2 the block reductions and stores,
 // bit 3 the key stores only.
@@ -396,14 +409,13 @@ static_assert(q8_seam_fits(8, false) && q8_seam_fits(8, true) && q8_seam_fits(10
 // One more LDS-DMA op per wave and group: the 64 mask words of the wave's 32
 // queries x the slot's 2 blocks, laid out [block][query j][half n] so a lane
 // reads its two queries' words of a block with one ds_read_b64.
-// LIVE (PAIR schedule; a batch that is not a multiple of 256 queries): a wave
-// whose 32 queries all lie at or past a.nq_live -- the padding of the last
+// LIVE (PAIR; a batch that is not a multiple of 256 queries): a wave whose 32 queries all lie at or past a.nq_live -- the padding of the last
 // query group -- reads no fragments and issues no MFMA or reduction; it still
 // issues its share of every slot's DMA and its key stores (+inf), so each
 // wave's vector-memory counts, which the ring's vmcnt waits rely on, are those
 // of the full schedule.  A batch of 64 queries runs the MFMAs of 2 waves
 // instead of 8 (the HBM stream of the plane is then the bound).
-// SEAM (PAIR, PF = 1; option q8_sched = 1, the default; 0 = the in-order slot
+// SEAM (PAIR; option q8_sched = 1, the default; 0 = the in-order slot
 // loop): the seamless ring.  The in-order schedule ends every slot with a tail
 // that all 8 waves run together -- the second block's reduction behind the
 // slot's last MFMA, the vmcnt wait, the barrier, then the next slot's first
@@ -425,8 +437,8 @@ static_assert(q8_seam_fits(8, false) && q8_seam_fits(8, true) && q8_seam_fits(10
 //     combine and key store to chunk KS; the slot's second valid word, scale
 //     and L2 norms are carried across the iteration.
 // The same MFMAs, fragments, DMA pieces and keys as the in-order schedule.
-template <int NC, int RB, bool ISL2, bool STAG = false, bool BQ = false, int PF = 1, int DBG = 0, bool LIVE = false,
-          bool MASK = false, bool SEAM = false>
+template <int NC, int RB, bool ISL2, bool BQ = false, int DBG = 0, bool LIVE = false, bool MASK = false,
+          bool SEAM = false>
 __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
     constexpr int NPB = 2 * NC;                     // 1 KiB pieces per 32-row block
     constexpr int SLOT = RB * NPB * 1024;           // bytes per ring slot
@@ -437,17 +449,16 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
     constexpr int NT = RB * NC;                     // chunks per slot
     constexpr int P0 = P + 2 + (ISL2 ? 1 : 0) + (MASK ? 1 : 0);  // vector-memory ops per group, per wave
     static_assert(P0 < NC, "the deferred key store must follow the slot's DMA pieces");
-    static_assert(PF >= 1 && PF + 1 < NC, "prefetch distance");
-    static_assert(!STAG || RB == 2, "the stagger defers a slot's second block");
-    static_assert(!BQ || (!ISL2 && !STAG), "BQ: integer maxima, in-order schedule");
-    static_assert(!LIVE || (RB == 2 && !STAG && !BQ && DBG == 0), "LIVE: the paired in-order schedule");
-    static_assert(!MASK || (RB == 2 && !STAG && !BQ && !ISL2 && DBG == 0), "MASK: paired dot / cosine keys");
-    static_assert(!SEAM || (RB == 2 && !STAG && !BQ && !MASK && PF == 1), "SEAM: the paired in-order variants, PF = 1");
+    static_assert(!BQ || !ISL2, "BQ: integer maxima");
+    static_assert(!LIVE || (RB == 2 && !BQ && DBG == 0), "LIVE: the paired schedules");
+    static_assert(!MASK || (RB == 2 && !BQ && !ISL2 && DBG == 0), "MASK: paired dot / cosine keys");
+    static_assert(!SEAM || (RB == 2 && !BQ && !MASK), "SEAM: the paired variants");
+    static_assert(q8_key_lds(NC, RB, ISL2, MASK) <= 160 * 1024, "the rings fit the CU's LDS");
     static_assert(!SEAM || q8_seam_fits(NC, ISL2), "SEAM: group t+2 is issued between the barrier and the slot's end");
     constexpr int XB = q8_seam_xb(NC), RD = Q8_SEAM_RD, KS = Q8_SEAM_KS;
     constexpr int X0 = 1;                           // chunk of the slot's extra LDS reads
     constexpr int XE = 2 + (ISL2 ? 2 * RB : 0) + (MASK ? 2 : 0);  // extra reads: valid words, scales (+ norms / masks)
-    constexpr int NBUF = 3;
+    constexpr int NBUF = Q8_NBUF;
     extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
 
     const int tid = threadIdx.x;
@@ -478,7 +489,7 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
     }
     const float sqA = BQ ? 1.f : a.qscale[q0 + (lane & 15)];
     const float sqB = BQ ? 1.f : a.qscale[q0 + 16 + (lane & 15)];
-    constexpr bool PAIR = RB == 2 && !STAG;
+    constexpr bool PAIR = RB == 2;
     // PAIR: the query of the lane's combined key (group G: half G >> 1)
     const float sqO = (BQ || !PAIR) ? 1.f : a.qscale[q0 + (lane & 15) + 16 * (lane >> 5)];
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): retire the query loads before the DMA ring
@@ -493,11 +504,12 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
     // per-wave rings of 4 entries (step & 3): valid words [8][4][16 B], block
     // scales [8][4][16 B], L2 norms [8][4][RB * 128 B]; every wave loads its own
     // copy, so every wave issues the same vector-memory ops per step
+    // (q8_key_lds counts these bytes)
     const unsigned vring = ring + NBUF * SLOT + (unsigned)wave * 64u;
-    const unsigned sring = ring + NBUF * SLOT + 512u + (unsigned)wave * 64u;
-    const unsigned xnring = ring + NBUF * SLOT + 1024u + (unsigned)wave * (unsigned)(4 * RB * 128);
+    const unsigned sring = ring + NBUF * SLOT + Q8_VS_RING + (unsigned)wave * 64u;
+    const unsigned xnring = ring + NBUF * SLOT + 2 * Q8_VS_RING + (unsigned)wave * q8_norm_wave(RB);
     // MASK: [8 waves][4 steps][64 words] per-query mask words (after the valid / scale rings)
-    const unsigned mring = ring + NBUF * SLOT + 1024u + (unsigned)wave * 1024u;
+    const unsigned mring = ring + NBUF * SLOT + 2 * Q8_VS_RING + (unsigned)wave * Q8_MASK_WAVE;
     const int64_t tile0 = (s0 * RB * 32) >> 8;
     const __amdgpu_buffer_rsrc_t xrs =
         __builtin_amdgcn_make_buffer_rsrc((void*)(a.X8 + tile0 * TILE_B), (short)0, -1, 0x00020000);
@@ -546,18 +558,11 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
     // lane (i = lane&15, kq = lane>>4) reads row 16m+i, columns 64c+16kq..+15
     // = piece 2c + (kq>>1), bytes 16(kq&1).. of the row (linear image)
     const unsigned l16 = (unsigned)(((lane >> 5) & 1) * 1024 + (lane & 15) * 32 + 16 * ((lane >> 4) & 1));
-    constexpr int NB2 = PF + 1;
-    i32x4_t B2[NB2][2];  // A fragments [chunk % NB2][row half m]
-    // the first PF chunks of a slot, right after its barrier
+    i32x4_t B2[2][2];  // A fragments [chunk % 2][row half m], read one chunk ahead
+    // the first chunk of a slot, right after its barrier
     auto head_reads = [&](unsigned sbh) {
-        static_for<0, PF>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            if constexpr (j < NT) {
-                constexpr int o = (j / NC * NPB + 2 * (j % NC)) * 1024;
-                B2[j % NB2][0] = lds_ld16_o<o>(sbh);
-                B2[j % NB2][1] = lds_ld16_o<o + 512>(sbh);
-            }
-        });
+        B2[0][0] = lds_ld16_o<0>(sbh);
+        B2[0][1] = lds_ld16_o<512>(sbh);
     };
     if (nsteps > 0) {
         issue_group(0, 0);
@@ -626,9 +631,6 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
         }
         a.key[(q0 + (lane & 15) + 16 * (lane >> 5)) * a.ldk + gbA + ((lane >> 4) & 1)] = key;
     };
-    // stores issued in slot t (the deferred finish + block 0's), for vmcnt
-    auto stores_in = [&](int t) -> int { return (t > 0 ? 1 : 0) + (PAIR ? 0 : RB - 1); };
-    constexpr int SPS = PAIR ? 1 : RB;  // key stores per slot
     // a block's reduction over its rows (accumulators ac, valid word vw_, scale
     // sb_, L2 norms xa_/xb_) -> the lane's partial keys (p0, p1)
     auto reduce = [&](const i32x4_t (&ac)[2][2], uint32_t vw_, float sb_, const f32x4_t& xa_, const f32x4_t& xb_,
@@ -732,18 +734,14 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
         r0 = rr[0];
         r1 = rr[1];
     };
+    // key stores issued in slot t (the deferred finish of slot t-1), for vmcnt
+    auto stores_in = [](int t) -> int { return t > 0 ? 1 : 0; };
     // PAIR: the pending slot's raw partials ("no valid row" until a block is
     // reduced: a LIVE wave without queries stores +inf keys)
     constexpr uint32_t PNONE = ISL2 ? 0x7f800000u : (uint32_t)Q8_NONE;
     uint32_t pA0 = PNONE, pA1 = PNONE, pB0 = PNONE, pB1 = PNONE;
     float psA = 0.f, psB = 0.f;                    // and its block scales
     i32x4_t acc[RB][2][2];
-    // STAG, waves 4-7: the previous slot's last block is reduced late, from its
-    // accumulators (kept: acc[1] is rewritten only from chunk NC on) and these
-    const bool late = STAG && wave >= 4;
-    uint32_t dvw = 0;
-    float dsb = 0.f;
-    f32x4_t dxa = {0.f, 0.f, 0.f, 0.f}, dxb = {0.f, 0.f, 0.f, 0.f};
     // static priority for the younger half of the SIMD pairs (MI355X_MICROARCH.md,
     // two waves per SIMD, item 4): one s_setprio before the loop, none inside
     if (a.prio && wave >= 4) __builtin_amdgcn_s_setprio(1);
@@ -777,7 +775,7 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
     // ---------------------------------------------------------------------
     auto seam_loop = [&](auto actc) {
     constexpr bool ACT = decltype(actc)::value;
-    static_assert(NT % NB2 == 0, "the fragment sets continue across the slot boundary");
+    static_assert(NT % 2 == 0, "the fragment sets continue across the slot boundary");
     int cur = 0;
     for (int t = 0; t < nsteps; t++) {
         const int nxt = cur == NBUF - 1 ? 0 : cur + 1;
@@ -812,8 +810,8 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
             if constexpr (tt + 1 < NT) {
                 if constexpr (ACT) {
                     constexpr int o1 = ((tt + 1) / NC * NPB + 2 * ((tt + 1) % NC)) * 1024;
-                    B2[(tt + 1) % NB2][0] = lds_ld16_o<o1>(sbase);
-                    B2[(tt + 1) % NB2][1] = lds_ld16_o<o1 + 512>(sbase);
+                    B2[(tt + 1) % 2][0] = lds_ld16_o<o1>(sbase);
+                    B2[(tt + 1) % 2][1] = lds_ld16_o<o1 + 512>(sbase);
                 }
                 qs_wait_lgkm<2 + (tt == X0 ? XE : 0)>();
             } else {
@@ -827,7 +825,7 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
                     qs_wait_lgkm<0>();
                 }
             }
-            asm volatile("" : "+v"(B2[tt % NB2][0]), "+v"(B2[tt % NB2][1]));
+            asm volatile("" : "+v"(B2[tt % 2][0]), "+v"(B2[tt % 2][1]));
             if constexpr (tt == X0 + 1 && ACT) {
                 if constexpr (ISL2) asm volatile("" : "+v"(vwv), "+v"(sbv), "+v"(xa[0]), "+v"(xb[0]), "+v"(xa[1]), "+v"(xb[1]));
                 else asm volatile("" : "+v"(vwv), "+v"(sbv));
@@ -838,12 +836,12 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
             for (int m = 0; m < 2; m++)
 #pragma unroll
                 for (int n = 0; n < 2; n++) {
-                    if constexpr (DBG & 2) { acc[rb][m][n] = B2[tt % NB2][m]; continue; }
+                    if constexpr (DBG & 2) { acc[rb][m][n] = B2[tt % 2][m]; continue; }
                     if constexpr (c == 0)
-                        acc[rb][m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(B2[tt % NB2][m], Qf[2 * c + n],
+                        acc[rb][m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(B2[tt % 2][m], Qf[2 * c + n],
                                                                               i32x4_t{0, 0, 0, 0}, 0, 0, 0);
                     else
-                        acc[rb][m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(B2[tt % NB2][m], Qf[2 * c + n],
+                        acc[rb][m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(B2[tt % 2][m], Qf[2 * c + n],
                                                                               acc[rb][m][n], 0, 0, 0);
                 }
             // the previous slot's second block: its reduction from acc[1] ...
@@ -936,17 +934,16 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
                     }
                 }
             }
-            if constexpr (tt + PF < NT && ACT) {
-                constexpr int o1 = ((tt + PF) / NC * NPB + 2 * ((tt + PF) % NC)) * 1024;
-                B2[(tt + PF) % NB2][0] = lds_ld16_o<o1>(sbase);
-                B2[(tt + PF) % NB2][1] = lds_ld16_o<o1 + 512>(sbase);
+            if constexpr (tt + 1 < NT && ACT) {
+                constexpr int o1 = ((tt + 1) / NC * NPB + 2 * ((tt + 1) % NC)) * 1024;
+                B2[(tt + 1) % 2][0] = lds_ld16_o<o1>(sbase);
+                B2[(tt + 1) % 2][1] = lds_ld16_o<o1 + 512>(sbase);
             }
-            // reads younger than chunk tt's: the chunks up to tt + PF, and the
-            // extras (issued at the start of step X0) while tt < X0 + PF
-            constexpr int ahead = (NT - 1 - tt) < PF ? (NT - 1 - tt) : PF;
-            qs_wait_lgkm<2 * ahead + ((tt >= X0 && tt < X0 + PF) ? XE : 0)>();
-            asm volatile("" : "+v"(B2[tt % NB2][0]), "+v"(B2[tt % NB2][1]));
-            if constexpr (tt == X0 + PF) {
+            // reads younger than chunk tt's: the next chunk's two, and the
+            // extras (issued at the start of step X0) at tt = X0
+            qs_wait_lgkm<(tt + 1 < NT ? 2 : 0) + (tt == X0 ? XE : 0)>();
+            asm volatile("" : "+v"(B2[tt % 2][0]), "+v"(B2[tt % 2][1]));
+            if constexpr (tt == X0 + 1) {
                 if constexpr (ISL2) {
                     asm volatile("" : "+v"(vwv), "+v"(sbv), "+v"(xa[0]), "+v"(xb[0]));
                     if constexpr (RB == 2) asm volatile("" : "+v"(xa[RB - 1]), "+v"(xb[RB - 1]));
@@ -961,12 +958,12 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
             for (int m = 0; m < 2; m++)
 #pragma unroll
                 for (int n = 0; n < 2; n++) {
-                    if constexpr (DBG & 2) { acc[rb][m][n] = B2[tt % NB2][m]; continue; }
+                    if constexpr (DBG & 2) { acc[rb][m][n] = B2[tt % 2][m]; continue; }
                     if constexpr (c == 0)
-                        acc[rb][m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(B2[tt % NB2][m], Qf[2 * c + n],
+                        acc[rb][m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(B2[tt % 2][m], Qf[2 * c + n],
                                                                               i32x4_t{0, 0, 0, 0}, 0, 0, 0);
                     else
-                        acc[rb][m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(B2[tt % NB2][m], Qf[2 * c + n],
+                        acc[rb][m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(B2[tt % 2][m], Qf[2 * c + n],
                                                                               acc[rb][m][n], 0, 0, 0);
                 }
             // DMA of group t+2: one piece per chunk
@@ -976,60 +973,37 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
             // the previous slot's last block: cross-lane combine + key store
             if constexpr (tt == P0 && !(DBG & 4)) {
                 if (t > 0) {
-                    if constexpr (PAIR) {
-                        finish2(pA0, pA1, pB0, pB1, psA, psB, gbp);
-                    } else {
-                        if (late) reduce(acc[RB - 1], dvw, dsb, dxa, dxb, mp0, mp1);
-                        finish(mp0, mp1, gbp);
-                    }
+                    if constexpr (PAIR) finish2(pA0, pA1, pB0, pB1, psA, psB, gbp);
+                    else finish(mp0, mp1, gbp);
                 }
             }
             // PAIR: block 0's partials beside block 1's MFMAs (stored with block 1)
             if constexpr (PAIR && tt == NC + 1 && !(DBG & 4) && ACT) reduce_raw(acc[0], vwv.x, sbv.x, xa[0], xb[0], pA0, pA1, mw0);
-            // RB = 2: block 0 is reduced and stored beside block 1's MFMAs
-            if constexpr (RB == 2 && !PAIR && tt == NC + 1 && !(DBG & 4)) {
-                if (!late) {
-                    float p0, p1;
-                    reduce(acc[0], vwv.x, sbv.x, xa[0], xb[0], p0, p1);
-                    finish(p0, p1, (s0 + t) * RB);
-                }
-            }
-            if constexpr (STAG && tt == NC + P0) {
-                if (late) {
-                    float p0, p1;
-                    reduce(acc[0], vwv.x, sbv.x, xa[0], xb[0], p0, p1);
-                    finish(p0, p1, (s0 + t) * RB);
-                }
-            }
         });
-        if (late) {
-            dvw = vwv.y;
-            dsb = sbv.y;
-            dxa = xa[RB - 1];
-            dxb = xb[RB - 1];
-        } else if constexpr (PAIR && !(DBG & 4)) {
+        if constexpr (PAIR && !(DBG & 4)) {
             if constexpr (ACT) {
                 reduce_raw(acc[1], vwv.y, sbv.y, xa[1], xb[1], pB0, pB1, mw1);
                 psA = sbv.x;
                 psB = sbv.y;
             }
-        } else if constexpr (!(DBG & 4)) {
-            reduce(acc[RB - 1], RB == 2 ? vwv.y : vwv.x, RB == 2 ? sbv.y : sbv.x, xa[RB - 1], xb[RB - 1], mp0, mp1);
+        } else if constexpr (!(DBG & 4)) {  // RB = 1: the slot's one block
+            reduce(acc[0], vwv.x, sbv.x, xa[0], xb[0], mp0, mp1);
         } else {
 #pragma unroll
             for (int r = 0; r < RB; r++)
                 dbg_sink ^= acc[r][0][0][0] ^ acc[r][0][1][0] ^ acc[r][1][0][0] ^ acc[r][1][1][0];
         }
-        gbp = (s0 + t) * RB + (PAIR ? 0 : RB - 1);
+        gbp = (s0 + t) * RB;  // the slot's first block: its one key store covers the slot
         // ---- end of the slot: the next group must have landed (every wave) ----
         if (t + 1 < nsteps) {
             // this wave's vector-memory ops after group t+1, in issue order: the
-            // stores of slot t-1, the pieces of group t+2, the stores of slot t
-            // (RB per slot; slot 0 has RB - 1)
+            // store of slot t-1, the pieces of group t+2, the store of slot t
+            // (slot u > 0 issues one key store, the deferred finish of slot u-1;
+            // slot 0 issues none; the span's last two slots issue no group)
             if constexpr (DBG != 0) {
                 qs_wait_vm_c<0>();
             } else if (t >= 2 && t + 2 < nsteps) {
-                qs_wait_vm_c<2 * SPS + P0>();
+                qs_wait_vm_c<2 + P0>();
             } else {
                 const int y = (t >= 1 ? stores_in(t - 1) : 0) + stores_in(t) + (t + 2 < nsteps ? P0 : 0);
                 qs_wait_vm(y);
@@ -1059,7 +1033,6 @@ __global__ __launch_bounds__(512, 2) void k_q8_blockkey(Q8Args a) {
         } else if constexpr (PAIR) {
             finish2(pA0, pA1, pB0, pB1, psA, psB, gbp);
         } else {
-            if (late) reduce(acc[RB - 1], dvw, dsb, dxa, dxb, mp0, mp1);
             finish(mp0, mp1, gbp);
         }
     }

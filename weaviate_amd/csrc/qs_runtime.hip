@@ -40,56 +40,71 @@ int invert_lists(wv_index* idx, hipStream_t s, const uint32_t* cand, const int32
     return WV_OK;
 }
 
-// the int8 block-key pass (k_q8_blockkey, 512 <= dpb8 <= 1536) over a.nslots
-// ring slots for a.nqg 256-query groups, spans chosen as search_qs does
-// (XCD-aware groups, 4 GiB span planes, whole rounds of workgroups)
-int launch_q8_keys(wv_index* idx, hipStream_t s, Q8Args a, int dpb8, bool l2) {
-    const int NC8 = dpb8 / 64;
-    const int RB = dpb8 <= 768 ? 2 : 1;
-    int64_t nspans = 256 / std::gcd(256, a.nqg);
-    while ((int64_t)a.nqg * nspans < 256) nspans *= 2;
-    if (idx->spans_opt > 0) nspans = idx->spans_opt;
-    const int64_t max_sps = ((1ll << 32) - 2 * 256ll * dpb8) / ((int64_t)RB * 32 * dpb8);
-    nspans = std::max<int64_t>(nspans, (a.nslots + max_sps - 1) / max_sps);
-    if (idx->spans_opt <= 0) {
-        const int64_t unit = 256 / std::gcd(256, a.nqg);
-        nspans = (nspans + unit - 1) / unit * unit;
+// "set the dynamic-LDS limit, launch" of the block-key kernels
+template <typename A>
+static hipError_t launch_dyn_lds(void (*kern)(A), dim3 grid, unsigned threads, size_t lds, hipStream_t s, const A& a) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    kern<<<grid, threads, lds, s>>>(a);
+    return hipSuccess;
+}
+
+// f(std::integral_constant<int, V>) for the V of Vs equal to v; WV_ERR_UNSUPPORTED without one
+template <class F, int... Vs>
+static int pick_int(int v, std::integer_sequence<int, Vs...>, F&& f) {
+    int rc = WV_ERR_UNSUPPORTED;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+
+// k_q8_blockkey<NC, ...> for the variant bits FL = l2 | bq << 1 | seam << 2 |
+// live << 3 | mask << 4 and the DBG bits; `ok` is the list of instantiations
+// (42 in the product build), anything else is WV_ERR_UNSUPPORTED
+template <int NC, int FL, int DBG>
+static int launch_q8_variant(hipStream_t s, const Q8Args& a) {
+    constexpr int RB = NC <= 12 ? 2 : 1;
+    constexpr bool ISL2 = FL & 1, BQ = FL & 2, SEAM = FL & 4, LIVE = FL & 8, MASK = FL & 16;
+    constexpr bool ok = DBG != 0 ? NC == 12 && !ISL2 && !BQ && !LIVE && !MASK  // timing build: plain or SEAM
+                        : BQ     ? !ISL2 && !SEAM && !LIVE && !MASK
+                        : RB == 1 ? !SEAM && !LIVE && !MASK
+                        : MASK   ? !ISL2 && !SEAM
+                                 : true;  // RB = 2: {plain, LIVE, SEAM, SEAM + LIVE} x {l2, dot / cosine}
+    if constexpr (ok) {
+        HIPCHK(launch_dyn_lds(k_q8_blockkey<NC, RB, ISL2, BQ, DBG, LIVE, MASK, SEAM>,
+                              dim3((unsigned)((int64_t)a.nqg * a.nspans)), 512, q8_key_lds(NC, RB, ISL2, MASK), s, a));
+        return WV_OK;
+    } else {
+        return WV_ERR_UNSUPPORTED;
     }
-    nspans = std::max<int64_t>(1, std::min<int64_t>(nspans, a.nslots));
-    const int64_t sps = (a.nslots + nspans - 1) / nspans;
-    a.slots_per_span = (int)sps;
-    a.nspans = (int)((a.nslots + sps - 1) / sps);
-    const size_t lds = (size_t)3 * RB * 2 * NC8 * 1024 + 1024 + (l2 ? (size_t)8 * 4 * RB * 128 : 0);
-    dim3 grid((unsigned)((int64_t)a.nqg * a.nspans));
-    const bool seam = idx->q8_sched && !idx->q8_stag && idx->q8_pf == 1;
-#define WV_Q8K(NCV, RBV, L2V)                                                                                  \
-    do {                                                                                                       \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<NCV, RBV, L2V, false, false, 1>,                 \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                     \
-        k_q8_blockkey<NCV, RBV, L2V, false, false, 1><<<grid, 512, lds, s>>>(a);                                \
-    } while (0)
-// the paired kernel (two blocks per slot): the seamless ring unless q8_sched = 0, q8_stag or q8_pf = 2
-#define WV_Q8KP(NCV, L2V)                                                                                      \
-    do {                                                                                                       \
-        if (!seam) { WV_Q8K(NCV, 2, L2V); break; }                                                             \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<NCV, 2, L2V, false, false, 1, 0, false, false, true>, \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                     \
-        k_q8_blockkey<NCV, 2, L2V, false, false, 1, 0, false, false, true><<<grid, 512, lds, s>>>(a);          \
-    } while (0)
-#define WV_Q8KN(L2V)                                   \
-    switch (NC8) {                                     \
-    case 8: WV_Q8KP(8, L2V); break;                    \
-    case 10: WV_Q8KP(10, L2V); break;                  \
-    case 12: WV_Q8KP(12, L2V); break;                  \
-    case 16: WV_Q8K(16, 1, L2V); break;                \
-    case 20: WV_Q8K(20, 1, L2V); break;                \
-    case 24: WV_Q8K(24, 1, L2V); break;                \
-    default: return set_err(WV_ERR_UNSUPPORTED, "int8 keys: plane width %d", dpb8); \
-    }
-    if (l2) { WV_Q8KN(true); } else { WV_Q8KN(false); }
-#undef WV_Q8KN
-#undef WV_Q8KP
-#undef WV_Q8K
+}
+
+// the int8 block-key pass over a.nslots ring slots for a.nqg 256-query groups
+// (rt_index.h: Q8Variant); the only place that names a k_q8_blockkey
+// instantiation, so no other unit compiles the kernel
+int launch_q8_keys(hipStream_t s, Q8Args a, int dpb8, const Q8Variant& v) {
+    const KeyPlan plan = key_plan(a.nqg, a.nslots, dpb8 <= 768 ? 2 : 1, dpb8, v.spans, v.whole_rounds);
+    a.slots_per_span = plan.slots_per_span;
+    a.nspans = plan.nspans;
+    const int fl = (v.l2 ? 1 : 0) | (v.bq ? 2 : 0) | (v.seam ? 4 : 0) | (v.live ? 8 : 0) | (v.mask ? 16 : 0);
+#ifdef WV_QS_DBG
+    using DbgBits = std::make_integer_sequence<int, 10>;
+#else
+    using DbgBits = std::integer_sequence<int, 0>;
+#endif
+    using Widths = std::integer_sequence<int, 8, 10, 12, 16, 20, 24>;
+    using Flags = std::make_integer_sequence<int, 32>;
+    int rc = WV_ERR_UNSUPPORTED;
+    if (dpb8 % 64 == 0)
+        rc = pick_int(dpb8 / 64, Widths{}, [&](auto nc) {
+            return pick_int(fl, Flags{}, [&](auto f) {
+                return pick_int(v.dbg, DbgBits{}, [&](auto d) {
+                    return launch_q8_variant<decltype(nc)::value, decltype(f)::value, decltype(d)::value>(s, a);
+                });
+            });
+        });
+    if (rc == WV_ERR_UNSUPPORTED)
+        return set_err(WV_ERR_UNSUPPORTED, "int8 keys: plane width %d, variant bits %d, debug %d", dpb8, fl, v.dbg);
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return WV_OK;
 }
@@ -104,7 +119,7 @@ int launch_q8_keys(wv_index* idx, hipStream_t s, Q8Args a, int dpb8, bool l2) {
 bool pqa_keys_route(const wv_index* idx) {
     const bool q8 = idx->q8_planes && (idx->q8_opt || idx->q8_only);
     return idx->pqa_keys && q8 && !idx->q8_only && idx->dpb8 <= 768 && idx->metric != WV_METRIC_L2_SQUARED &&
-           !idx->q8_stag && idx->q8_shape != 32 && idx->sel_dbg <= 0;
+           idx->q8_shape != 32 && idx->sel_dbg <= 0;
 }
 
 int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const uint32_t* valid,
@@ -232,44 +247,23 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
         const bool w4 = !q8 && idx->dpb > QS_W4_DPB;
         const int w4_nb = NK == 64 ? 4 : 3;
         a.nqg = (int)(cn_pad / (q8wide ? 64 : (w4 || q8cp) ? 128 : QS_QPB));
-        int64_t nspans = 256 / std::gcd(256, a.nqg);
-        while ((int64_t)a.nqg * nspans < 256) nspans *= 2;
-        if (idx->spans_opt > 0) nspans = idx->spans_opt;
-        {   // a span's plane bytes (+ one tile of slack) must stay below 4 GiB (32-bit buffer offsets)
-            const int64_t row_b = q8 ? (int64_t)idx->dpb8 : (int64_t)idx->dpb * 2;
-            const int64_t slot_b = (int64_t)RB * 32 * row_b;
-            const int64_t max_sps = ((1ll << 32) - 2 * 256ll * row_b) / slot_b;
-            nspans = std::max<int64_t>(nspans, (nslots + max_sps - 1) / max_sps);
-        }
-        if (idx->spans_opt <= 0) {  // whole rounds of one workgroup per CU (10M x 1024: 5 spans = 320 groups -> 8)
-            const int64_t unit = 256 / std::gcd(256, a.nqg);
-            nspans = (nspans + unit - 1) / unit * unit;
-        }
-        nspans = std::max<int64_t>(1, std::min<int64_t>(nspans, nslots));
-        const int64_t sps = (nslots + nspans - 1) / nspans;
-        a.slots_per_span = (int)sps;
-        a.nspans = (int)((nslots + sps - 1) / sps);
+        // the spans (key_plan.h; k_q8_blockkey's launcher plans the same way)
+        const KeyPlan plan = key_plan(a.nqg, nslots, RB, q8 ? (int64_t)idx->dpb8 : (int64_t)idx->dpb * 2,
+                                      idx->spans_opt, true);
+        a.slots_per_span = plan.slots_per_span;
+        a.nspans = plan.nspans;
         const bool l2 = metric == L2;
         const size_t lds = q8wide ? (size_t)3 * 32 * 1024 + 1024 + (l2 ? (size_t)4 * 512 : 0)
                          : q8cp ? (size_t)3 * NC8 * 1024 + 1024 + (l2 ? (size_t)8 * 4 * 128 : 0)
-                         : q8 ? (size_t)3 * RB * 2 * NC8 * 1024 + 1024 + (l2 ? (size_t)8 * 4 * RB * 128 : 0) +
-                                    (pqk ? (size_t)8 * 1024 : 0)
+                         : q8 ? q8_key_lds(NC8, RB, l2, false)  // k_q8_blockkey32: k_q8_blockkey's rings
                          : w4 ? (size_t)w4_nb * (NK / 4) * 2048 + 256 + (l2 ? (size_t)4 * 4 * 128 : 0)
                               : (size_t)QS_NBUF * RB * NK * 1024 + 512 + (l2 ? (size_t)8 * 4 * RB * 128 : 0);
         dim3 grid((unsigned)((int64_t)a.nqg * a.nspans));
         if (phase != 2) {
         const bool time_it = idx->timing && c0 == 0;
         if (time_it) HIPCHK(hipEventRecord(idx->ev0, s));
-#define WV_QS(NKV, L2V)                                                                                        \
-    do {                                                                                                       \
-        HIPCHK(hipFuncSetAttribute((const void*)k_qs_blockkey<NKV, L2V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_qs_blockkey<NKV, L2V><<<grid, 512, lds, s>>>(a);                                                     \
-    } while (0)
-#define WV_QS3(NKV, L2V, D)                                                                                    \
-    do {                                                                                                       \
-        HIPCHK(hipFuncSetAttribute((const void*)k_qs_blockkey<NKV, L2V, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_qs_blockkey<NKV, L2V, D><<<grid, 512, lds, s>>>(a);                                                  \
-    } while (0)
+#define WV_QS(NKV, L2V) HIPCHK(launch_dyn_lds(k_qs_blockkey<NKV, L2V>, grid, 512, lds, s, a))
+#define WV_QS3(NKV, L2V, D) HIPCHK(launch_dyn_lds(k_qs_blockkey<NKV, L2V, D>, grid, 512, lds, s, a))
 #define WV_QSN(L2V)                                    \
     switch (NK) {                                      \
     case 8: WV_QS(8, L2V); break;                      \
@@ -279,71 +273,9 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
     case 40: WV_QS(40, L2V); break;                    \
     default: WV_QS(48, L2V); break;                    \
     }
-#define WV_QSW(NKV, L2V, NBV)                                                                                  \
-    do {                                                                                                       \
-        HIPCHK(hipFuncSetAttribute((const void*)k_qs_blockkey_w4<NKV, L2V, 2, NBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_qs_blockkey_w4<NKV, L2V, 2, NBV><<<grid, 256, lds, s>>>(a);                                          \
-    } while (0)
+#define WV_QSW(NKV, L2V, NBV) HIPCHK(launch_dyn_lds(k_qs_blockkey_w4<NKV, L2V, 2, NBV>, grid, 256, lds, s, a))
 #define WV_QSWN(L2V)                                   \
     if (NK == 64) WV_QSW(64, L2V, 4); else WV_QSW(96, L2V, 3);
-#define WV_Q8S(NCV, RBV, L2V, STV, PFV)                                                                        \
-    do {                                                                                                       \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<NCV, RBV, L2V, STV, false, PFV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_q8_blockkey<NCV, RBV, L2V, STV, false, PFV><<<grid, 512, lds, s>>>(q8a);                              \
-    } while (0)
-#define WV_Q8(NCV, RBV, L2V) do { if (idx->q8_pf == 2) WV_Q8S(NCV, RBV, L2V, false, 2); else WV_Q8S(NCV, RBV, L2V, false, 1); } while (0)
-// the paired kernel on the seamless ring (option q8_sched; q8_stag and q8_pf = 2 keep the in-order slot loop)
-#define WV_Q8E(NCV, L2V, LIVEV)                                                                                \
-    do {                                                                                                       \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<NCV, 2, L2V, false, false, 1, 0, LIVEV, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_q8_blockkey<NCV, 2, L2V, false, false, 1, 0, LIVEV, false, true><<<grid, 512, lds, s>>>(q8a);        \
-    } while (0)
-        const bool q8seam = idx->q8_sched && !idx->q8_stag && idx->q8_pf == 1;
-#ifdef WV_QS_DBG  // timing experiments (k_q8_blockkey DBG bits), not in the product build
-#define WV_Q8D(DV)                                                                                             \
-    do {                                                                                                       \
-        if (q8seam) {                                                                                          \
-            HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<12, 2, false, false, false, 1, DV, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            k_q8_blockkey<12, 2, false, false, false, 1, DV, false, false, true><<<grid, 512, lds, s>>>(q8a);  \
-            break;                                                                                             \
-        }                                                                                                      \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<12, 2, false, false, false, 1, DV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_q8_blockkey<12, 2, false, false, false, 1, DV><<<grid, 512, lds, s>>>(q8a);                           \
-    } while (0)
-#endif
-#define WV_Q8L(NCV, L2V)                                                                                       \
-    do {                                                                                                       \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<NCV, 2, L2V, false, false, 1, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_q8_blockkey<NCV, 2, L2V, false, false, 1, 0, true><<<grid, 512, lds, s>>>(q8a);                     \
-    } while (0)
-        // a partial last query group (batches that are not a multiple of 256):
-        // the padding's waves skip their MFMAs (LIVE)
-        const bool q8live = idx->q8_live && cn % QS_QPB != 0;
-// per-query keys (pqk: never L2, stag or the 32-wide shape)
-#define WV_Q8M(NCV, LIVEV)                                                                                     \
-    do {                                                                                                       \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<NCV, 2, false, false, false, 1, 0, LIVEV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_q8_blockkey<NCV, 2, false, false, false, 1, 0, LIVEV, true><<<grid, 512, lds, s>>>(q8a);           \
-    } while (0)
-#define WV_Q8T(NCV, L2V)                                                                                       \
-    do {                                                                                                       \
-        if constexpr (!L2V) {                                                                                  \
-            if (pqk) { if (q8live) WV_Q8M(NCV, true); else WV_Q8M(NCV, false); break; }                       \
-        }                                                                                                      \
-        if (idx->q8_stag) WV_Q8S(NCV, 2, L2V, true, 1);                                                        \
-        else if (q8seam) { if (q8live) WV_Q8E(NCV, L2V, true); else WV_Q8E(NCV, L2V, false); }                 \
-        else if (q8live) WV_Q8L(NCV, L2V);                                                                     \
-        else WV_Q8(NCV, 2, L2V);                                                                               \
-    } while (0)
-#define WV_Q8N(L2V)                                    \
-    switch (NC8) {                                     \
-    case 8: WV_Q8T(8, L2V); break;                     \
-    case 10: WV_Q8T(10, L2V); break;                   \
-    case 12: WV_Q8T(12, L2V); break;                   \
-    case 16: WV_Q8(16, 1, L2V); break;                 \
-    case 20: WV_Q8(20, 1, L2V); break;                 \
-    default: WV_Q8(24, 1, L2V); break;                 \
-    }
         idx->stats.last_route = q8 ? WV_ROUTE_QS_INT8 : w4 ? WV_ROUTE_QS_W4 : WV_ROUTE_QS_BF16;
         if (q8) {
             Q8Args q8a;
@@ -356,7 +288,7 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
             q8a.key = a.key;
             q8a.ldk = ldk;
             q8a.nslots = nslots;
-            q8a.slots_per_span = a.slots_per_span;
+            q8a.slots_per_span = a.slots_per_span;  // k_q8_blockkey32 / _cp; launch_q8_keys plans its own (the same)
             q8a.nspans = a.nspans;
             q8a.nqg = a.nqg;
             q8a.nq_live = cn;
@@ -366,20 +298,24 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
                 q8a.qmask_ld = idx->pqa_vq;
                 q8a.qmask_n = cn;
             }
-#ifdef WV_QS_DBG
+            // k_q8_blockkey's variant: two blocks per slot (RB8 = 2) run the
+            // per-query masked keys (pqk: dot / cosine), else the seamless ring
+            // (option q8_sched) or the in-order loop; a partial last query group
+            // (a batch that is not a multiple of 256) lets the padding's waves
+            // skip their MFMAs (LIVE).  One block per slot: the plain kernel.
+            Q8Variant q8v;
+            q8v.l2 = l2;
+            q8v.spans = idx->spans_opt;
+            if (RB8 == 2) {
+                q8v.mask = pqk && !l2;
+                q8v.seam = !q8v.mask && idx->q8_sched;
+                q8v.live = idx->q8_live && cn % QS_QPB != 0;
+            }
+#ifdef WV_QS_DBG  // timing experiments (k_q8_blockkey DBG bits), not in the product build
             const bool q8dbg = idx->sel_dbg > 0 && !l2 && NC8 == 12;
             if (q8dbg) {
-                switch (idx->sel_dbg) {
-                case 1: WV_Q8D(1); break;
-                case 2: WV_Q8D(2); break;
-                case 3: WV_Q8D(3); break;
-                case 4: WV_Q8D(4); break;
-                case 5: WV_Q8D(5); break;
-                case 6: WV_Q8D(6); break;
-                case 8: WV_Q8D(8); break;
-                case 9: WV_Q8D(9); break;
-                default: WV_Q8D(7); break;
-                }
+                q8v.dbg = idx->sel_dbg <= 9 ? idx->sel_dbg : 7;
+                q8v.live = false;
             }
 #else
             const bool q8dbg = false;
@@ -388,7 +324,9 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
             // 256-query padding of the MFMA work), the same keys
             const int qg = cn <= 16 ? 1 : 2;
             const bool gemv = idx->q8_gemv && !q8cp && !pqk && cn <= 32 && NC8 <= (qg == 1 ? 24 : 16) && nb < (1ll << 40);
-            if (q8dbg) {  // the timing build's launch above
+            if (q8dbg) {  // the timing build: always k_q8_blockkey
+                const int rc = launch_q8_keys(s, q8a, idx->dpb8, q8v);
+                if (rc) return rc;
             } else if (gemv) {
                 idx->stats.last_route = WV_ROUTE_Q8_GEMV;
                 const unsigned gg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (nb + 3) / 4));
@@ -408,11 +346,7 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
 #undef WV_Q8GQ
 #undef WV_Q8G
             } else if (idx->q8_shape == 32) {
-#define WV_Q832(NCV, RBV, L2V)                                                                                \
-    do {                                                                                                      \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey32<NCV, RBV, L2V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_q8_blockkey32<NCV, RBV, L2V><<<grid, 512, lds, s>>>(q8a);                                            \
-    } while (0)
+#define WV_Q832(NCV, RBV, L2V) HIPCHK(launch_dyn_lds(k_q8_blockkey32<NCV, RBV, L2V>, grid, 512, lds, s, q8a))
 #define WV_Q832N(L2V)                                  \
     switch (NC8) {                                     \
     case 8: WV_Q832(16, 2, L2V); break;                \
@@ -426,16 +360,8 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
 #undef WV_Q832N
 #undef WV_Q832
             } else if (q8cp) {
-#define WV_Q8CP(NCSV, L2V)                                                                                     \
-    do {                                                                                                       \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey_cp<NCSV, L2V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_q8_blockkey_cp<NCSV, L2V><<<grid, 512, lds, s>>>(q8a);                                               \
-    } while (0)
-#define WV_Q8CPW(NPV, L2V)                                                                                     \
-    do {                                                                                                       \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey_cp<16, L2V, NPV, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        k_q8_blockkey_cp<16, L2V, NPV, 4><<<grid, 256, lds, s>>>(q8a);                                         \
-    } while (0)
+#define WV_Q8CP(NCSV, L2V) HIPCHK(launch_dyn_lds(k_q8_blockkey_cp<NCSV, L2V>, grid, 512, lds, s, q8a))
+#define WV_Q8CPW(NPV, L2V) HIPCHK(launch_dyn_lds(k_q8_blockkey_cp<16, L2V, NPV, 4>, grid, 256, lds, s, q8a))
 #define WV_Q8CPN(L2V)                                  \
     switch (NC8) {                                     \
     case 32: WV_Q8CP(16, L2V); break;                  \
@@ -449,7 +375,10 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
 #undef WV_Q8CPN
 #undef WV_Q8CPW
 #undef WV_Q8CP
-            } else if (l2) { WV_Q8N(true); } else { WV_Q8N(false); }
+            } else {
+                const int rc = launch_q8_keys(s, q8a, idx->dpb8, q8v);
+                if (rc) return rc;
+            }
         } else if (w4) {
             if (l2) { WV_QSWN(true); } else { WV_QSWN(false); }
 #ifdef WV_QS_DBG  // timing experiments (k_qs_blockkey DBG bits), not in the product build
@@ -470,13 +399,6 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
 #undef WV_QS
 #undef WV_QSWN
 #undef WV_QSW
-#undef WV_Q8N
-#undef WV_Q8T
-#undef WV_Q8M
-#undef WV_Q8L
-#undef WV_Q8S
-#undef WV_Q8E
-#undef WV_Q8
         HIPCHK(hipGetLastError());
         if (time_it) { HIPCHK(hipEventRecord(idx->ev1, s)); idx->timed = 1; }
         idx->stats.mfma_launches++;

@@ -70,7 +70,6 @@ static int bq_begin(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t n
 static int bq_blockmin_i8(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_t g0, int F, int64_t nblk,
                           float* bm) {
     const int dpb8 = idx->dpb8b;
-    const int NC = dpb8 / 64;
     const int RB = dpb8 <= 768 ? 2 : 1;
     const int64_t Fp = round_up(F, 256);
     HIPCHK(idx->q8Qb.ensure((size_t)Fp * dpb8));
@@ -92,37 +91,12 @@ static int bq_blockmin_i8(wv_index* idx, hipStream_t s, const uint32_t* valid, i
     a.bq_bits = 64 * idx->words;
     a.nslots = nblk / RB;
     a.nqg = (int)(Fp / 256);
-    // whole rounds of one workgroup per CU
-    int64_t nspans = 256 / std::gcd((int64_t)256, (int64_t)a.nqg);
-    while ((int64_t)a.nqg * nspans < 256) nspans *= 2;
-    {   // a span's plane bytes below 4 GiB (32-bit buffer offsets)
-        const int64_t slot_b = (int64_t)RB * 32 * dpb8;
-        const int64_t max_sps = ((1ll << 32) - 2 * 256ll * dpb8) / slot_b;
-        nspans = std::max<int64_t>(nspans, (a.nslots + max_sps - 1) / max_sps);
-    }
-    nspans = std::max<int64_t>(1, std::min<int64_t>(nspans, a.nslots));
-    const int64_t sps = (a.nslots + nspans - 1) / nspans;
-    a.slots_per_span = (int)sps;
-    a.nspans = (int)((a.nslots + sps - 1) / sps);
-    const size_t lds = (size_t)3 * RB * 2 * NC * 1024 + 1024;
-    dim3 grid((unsigned)((int64_t)a.nqg * a.nspans));
-#define WV_BQ8(NCV, RBV)                                                                                        \
-    do {                                                                                                        \
-        HIPCHK(hipFuncSetAttribute((const void*)k_q8_blockkey<NCV, RBV, false, false, true>,                    \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-        k_q8_blockkey<NCV, RBV, false, false, true><<<grid, 512, lds, s>>>(a);                                  \
-    } while (0)
-    switch (NC) {
-    case 8: WV_BQ8(8, 2); break;
-    case 10: WV_BQ8(10, 2); break;
-    case 12: WV_BQ8(12, 2); break;
-    case 16: WV_BQ8(16, 1); break;
-    case 20: WV_BQ8(20, 1); break;
-    default: WV_BQ8(24, 1); break;
-    }
-#undef WV_BQ8
-    HIPCHK(hipGetLastError());
-    return WV_OK;
+    // the block minima keep the planner's own span count: no `spans` option,
+    // no rounding to whole rounds of workgroups
+    Q8Variant v;
+    v.bq = true;
+    v.whole_rounds = false;
+    return launch_q8_keys(s, a, dpb8, v);
 }
 
 // compile-time word count for the LDS-broadcast block-minima kernel and the
@@ -1096,7 +1070,11 @@ static int pq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const
     a.nslots = nslots;
     a.nqg = (int)(nq_pad / QS_QPB);
     if (idx->timing) HIPCHK(hipEventRecord(idx->ev0, s));
-    rc = launch_q8_keys(idx, s, a, dpb8, true);
+    Q8Variant v;  // always l2, never LIVE, prio 0
+    v.l2 = true;
+    v.seam = RB == 2 && idx->q8_sched;
+    v.spans = idx->spans_opt;
+    rc = launch_q8_keys(s, a, dpb8, v);
     if (rc) return rc;
     if (idx->timing) HIPCHK(hipEventRecord(idx->ev1, s));
     idx->stats.last_group_queries = (uint64_t)nq;

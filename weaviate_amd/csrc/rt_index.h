@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/wv_knn.h"
+#include "key_plan.h"
 #include "kernels.hip"
 #include "bq_kernels.hip"
 #include "pq_kernels.hip"
@@ -152,8 +153,6 @@ struct wv_index {
     int q8_opt = 1;                 // option q8: block keys from the int8 plane (1) or the bf16 plane (0)
     int q8_R = 0;                   // option q8_R: candidate lists for int8 keys (0: R = 8, 448 blocks)
     int q8_shape = 16;              // option q8_shape: 16 = v_mfma_i32_16x16x64_i8 kernel, 32 = 32x32x32
-    int q8_stag = 0;
-    int q8_pf = 1;                  // option q8_pf: A-fragment reads 1 or 2 chunks ahead                // option q8_stag: waves 4-7 reduce each block P0 chunks late (RB = 2)
     int q8_sched = 1;               // option q8_sched: the paired int8 key kernel's slot loop: 1 = seamless ring (SEAM), 0 = in-order
     int q8_gemv = 1;                // option q8_gemv: batches of <= 32 queries stream the int8 plane through registers (k_q8_gemv)
     int q8_live = 1;                // option q8_live: waves of a partial query group's padding skip their MFMAs (k_q8_blockkey LIVE)
@@ -354,7 +353,25 @@ int qs_R_flat(int k);
 int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const uint32_t* valid, uint64_t* o_ids,
               float* o_d, int32_t* o_n, int32_t* o_flags, int phase = 0, float* topA = nullptr,
               const float* gA = nullptr, const float* gE = nullptr, int W = 0);
-int launch_q8_keys(wv_index* idx, hipStream_t s, Q8Args a, int dpb8, bool l2);
+// the one launcher of k_q8_blockkey (512 <= dpb8 <= 1536: RB = 2 up to 768
+// columns, 1 above): plans a's spans (key_plan.h), sizes the LDS rings and
+// launches the variant v names; WV_ERR_UNSUPPORTED for a width or a combination
+// that is not instantiated (SEAM, LIVE and MASK are RB = 2 variants; MASK is
+// dot / cosine on the in-order loop; BQ takes none of the others)
+struct Q8Variant {
+    bool l2 = false;    // l2-squared keys (dot / cosine otherwise)
+    bool bq = false;    // BQ +-1 planes: minimum hamming distance per block
+    bool seam = false;  // the seamless ring instead of the in-order slot loop
+    bool live = false;  // padding waves of a partial query group skip their MFMAs (a.nq_live)
+    bool mask = false;  // per-query row bitmaps (a.qmask)
+    int spans = 0;             // the `spans` option (0: the planner's choice)
+    bool whole_rounds = true;  // round the spans up to whole rounds of workgroups
+    // DBG bits of a timing experiment (NC = 12, dot / cosine); instantiated in
+    // a -DWV_QS_DBG build of qs_runtime.hip only, 0 otherwise (the field is
+    // unconditional: the units of a timing build differ in their -D flags)
+    int dbg = 0;
+};
+int launch_q8_keys(hipStream_t s, Q8Args a, int dpb8, const Q8Variant& v);
 int invert_lists(wv_index* idx, hipStream_t s, const uint32_t* cand, const int32_t* ncand, const int32_t* flags,
                  int64_t cn, int L, int64_t nb);
 // qs_exact.hip
