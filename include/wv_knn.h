@@ -39,6 +39,7 @@ extern "C" {
 #define WV_METRIC_DOT 1            /* "dot"        distancer/dot_product.go         */
 #define WV_METRIC_COSINE_DOT 2     /* "cosine-dot" distancer/cosine_dist.go         */
 #define WV_METRIC_HAMMING 3        /* "hamming"    distancer/hamming.go             */
+#define WV_METRIC_MANHATTAN 4      /* "manhattan"  distancer/manhattan.go           */
 
 /* compression: flatent.UserConfig (entities/vectorindex/flat/config.go:43-82) */
 #define WV_COMPRESSION_NONE 0
@@ -585,6 +586,7 @@ typedef struct wv_stats {
 #define WV_ROUTE_PQ_INT8 8   /* PQ: k_q8_blockkey over the centred int8 reconstruction plane (l2-squared) */
 #define WV_ROUTE_Q8_GEMV 9   /* k_q8_gemv (int8 block keys of <= 32 queries streamed through registers) */
 #define WV_ROUTE_RQ8_INT8 10 /* flat rq-8: k_rq8_keys (exact rq-8 block minima on the integer MFMA) */
+#define WV_ROUTE_L1_TILE 11  /* manhattan: k_l1_rows (register-tiled exact L1 of every row, then the heap replay) */
 int wv_index_stats(wv_index *idx, wv_stats *out);
 
 /* Diagnostic hook (tests): the last MFMA batch's candidates [nq][KP]:

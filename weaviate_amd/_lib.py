@@ -23,6 +23,7 @@ METRIC_L2 = 0
 METRIC_DOT = 1
 METRIC_COSINE = 2
 METRIC_HAMMING = 3
+METRIC_MANHATTAN = 4
 
 VARIANT_AUTO = 0
 VARIANT_AVX256 = 1
@@ -90,7 +91,7 @@ class WvStats(C.Structure):
 
 # wv_stats.last_route (include/wv_knn.h WV_ROUTE_*)
 ROUTES = {0: "none", 1: "qs_bf16", 2: "qs_w4", 3: "qs_int8", 4: "f32_select", 5: "gemv", 6: "bq_int8", 7: "bq_valu",
-          8: "pq_int8", 9: "q8_gemv", 10: "rq8_int8"}
+          8: "pq_int8", 9: "q8_gemv", 10: "rq8_int8", 11: "l1_tile"}
 
 
 P = C.c_void_p

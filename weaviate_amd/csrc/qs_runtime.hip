@@ -641,7 +641,7 @@ extern "C" int wv_index_shard_phase1(wv_index* idx, const float* d_queries, int6
     idx->qs_phase_nq = 0;
     const bool qs = idx->compression == WV_COMPRESSION_NONE && (idx->qs_planes || idx->q8_only) && !idx->has_nonfinite &&
                     (idx->kernel_opt == 0 || idx->kernel_opt == 7) && !idx->force_replay && qs_R(k) > 0 &&
-                    idx->metric != WV_METRIC_HAMMING && idx->dims != 0 && idx->npresent > 0 && nq > 0;
+                    metric_bilinear(idx->metric) && idx->dims != 0 && idx->npresent > 0 && nq > 0;
     if (!qs) return set_err(WV_ERR_UNSUPPORTED, "two-phase shard search: not on the block-key path");
     if (d != idx->dims)
         return set_err(WV_ERR_VECTOR_LENGTH, "%lld vs %d: vector lengths don't match", (long long)d, idx->dims);

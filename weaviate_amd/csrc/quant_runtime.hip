@@ -222,7 +222,7 @@ static bool bq_fast(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_t
                     int32_t* out_n, int32_t* skip, int* rc) {
     *rc = WV_OK;
     const int nw = bq_nw(idx);
-    if (!idx->bq_fast || bq_blk(idx) != 32 || k > BQF_K || idx->metric == WV_METRIC_HAMMING ||
+    if (!idx->bq_fast || bq_blk(idx) != 32 || k > BQF_K || !metric_bilinear(idx->metric) ||
         (nw != 8 && nw != 12 && nw != 16 && nw != 24))
         return false;
     const bool v5 = idx->variant == WV_VARIANT_AVX512;
@@ -268,6 +268,7 @@ static int bq_rescore(wv_index* idx, hipStream_t s, const uint64_t* ids, const i
     case WV_METRIC_L2_SQUARED: if (v5) WV_RS(L2, AVX512); else WV_RS(L2, AVX256); break;
     case WV_METRIC_DOT: if (v5) WV_RS(DOT, AVX512); else WV_RS(DOT, AVX256); break;
     case WV_METRIC_COSINE_DOT: if (v5) WV_RS(COSINE, AVX512); else WV_RS(COSINE, AVX256); break;
+    case WV_METRIC_MANHATTAN: WV_RS(MANHATTAN, AVX256); break;
     default: WV_RS(HAMMING, AVX256); break;
     }
 #undef WV_RS
@@ -1317,6 +1318,7 @@ static int search_hnsw(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
         case WV_METRIC_L2_SQUARED: if (v5) WV_RS(L2, AVX512); else WV_RS(L2, AVX256); break;
         case WV_METRIC_DOT: if (v5) WV_RS(DOT, AVX512); else WV_RS(DOT, AVX256); break;
         case WV_METRIC_COSINE_DOT: if (v5) WV_RS(COSINE, AVX512); else WV_RS(COSINE, AVX256); break;
+        case WV_METRIC_MANHATTAN: WV_RS(MANHATTAN, AVX256); break;
         default: WV_RS(HAMMING, AVX256); break;
         }
 #undef WV_RS
@@ -1599,6 +1601,7 @@ extern "C" int wv_index_quant_rescore(wv_index* idx, const uint64_t* d_cand_ids,
     case WV_METRIC_L2_SQUARED: if (v5) WV_RS(L2, AVX512); else WV_RS(L2, AVX256); break;
     case WV_METRIC_DOT: if (v5) WV_RS(DOT, AVX512); else WV_RS(DOT, AVX256); break;
     case WV_METRIC_COSINE_DOT: if (v5) WV_RS(COSINE, AVX512); else WV_RS(COSINE, AVX256); break;
+    case WV_METRIC_MANHATTAN: WV_RS(MANHATTAN, AVX256); break;
     default: WV_RS(HAMMING, AVX256); break;
     }
 #undef WV_RS

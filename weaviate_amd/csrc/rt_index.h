@@ -30,6 +30,7 @@
 #include "../../include/wv_knn.h"
 #include "key_plan.h"
 #include "kernels.hip"
+#include "l1_kernels.hip"
 #include "bq_kernels.hip"
 #include "pq_kernels.hip"
 #include "kernels_bf3.hip"
@@ -79,6 +80,11 @@ struct DBuf {
 };
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+// l2-squared, dot, cosine: a bilinear form, so the block-key, GEMV and MFMA routes can approximate it.
+// hamming and manhattan are not: every query of theirs takes the all-rows exact path (run_replay).
+static inline bool metric_bilinear(int m) {
+    return m == WV_METRIC_L2_SQUARED || m == WV_METRIC_DOT || m == WV_METRIC_COSINE_DOT;
+}
 // u32 words per row of the PQ code store (256-row tiles of 16-segment groups,
 // pq_kernels.hip); cap is a multiple of 256
 static inline int64_t pq_mwp(int m) { return (int64_t)((m + 15) / 16) * 4; }
@@ -293,6 +299,7 @@ struct wv_index {
     wv_batcher* batcher = nullptr;
     // written by set_option under mu, read by the batcher leader without it
     std::atomic<int64_t> batch_window_us{1000}, batch_max{4096};
+    int l1_tile = -1;  // manhattan all-rows kernel: -1 auto (L1_TILE_MIN), 0 k_exact_rows, 1 k_l1_rows
     int gemv_max = 8, gemv_wg = 1024, exact_multi = 1;  // batches up to this many queries take the GEMV select kernel (kver 6)
 };
 

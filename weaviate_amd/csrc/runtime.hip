@@ -85,7 +85,7 @@ static void set_dims(wv_index* idx, int64_t d) {
 
 extern "C" int wv_index_create(const wv_config* cfg, wv_index** out) {
     if (!cfg || !out) return set_err(WV_ERR_INVALID, "invalid config: nil");
-    if (cfg->metric < 0 || cfg->metric > WV_METRIC_HAMMING)
+    if (cfg->metric < 0 || cfg->metric > WV_METRIC_MANHATTAN)
         return set_err(WV_ERR_INVALID, "invalid config: unknown distance metric %d", cfg->metric);
     if (cfg->compression != WV_COMPRESSION_NONE && cfg->compression != WV_COMPRESSION_BQ &&
         cfg->compression != WV_COMPRESSION_PQ && cfg->compression != WV_COMPRESSION_RQ8 &&
@@ -95,6 +95,14 @@ extern "C" int wv_index_create(const wv_config* cfg, wv_index** out) {
     if ((cfg->compression == WV_COMPRESSION_RQ8 || cfg->compression == WV_COMPRESSION_RQ1) &&
         cfg->metric == WV_METRIC_HAMMING)
         return set_err(WV_ERR_UNSUPPORTED, "Distance not supported yet hamming");
+    // the same switch, and scalar_quantization.go:49-57, have no manhattan arm
+    if ((cfg->compression == WV_COMPRESSION_RQ8 || cfg->compression == WV_COMPRESSION_RQ1 ||
+         cfg->compression == WV_COMPRESSION_SQ) &&
+        cfg->metric == WV_METRIC_MANHATTAN)
+        return set_err(WV_ERR_UNSUPPORTED, "Distance not supported yet manhattan");
+    // the reference runs PQ over manhattan through the provider's Step; this engine does not yet
+    if (cfg->compression == WV_COMPRESSION_PQ && cfg->metric == WV_METRIC_MANHATTAN)
+        return set_err(WV_ERR_UNSUPPORTED, "pq: the manhattan distance is not supported");
     if (cfg->dims > RQ_MAXD - 64 && (cfg->compression == WV_COMPRESSION_RQ8 || cfg->compression == WV_COMPRESSION_RQ1))
         return set_err(WV_ERR_UNSUPPORTED, "rq: dimensions > %d not supported", RQ_MAXD - 64);
     HIPCHK(hipSetDevice(cfg->device));
@@ -109,7 +117,7 @@ extern "C" int wv_index_create(const wv_config* cfg, wv_index** out) {
     idx->root_path = cfg->root_path ? cfg->root_path : "";
     // block-key path for the exact fp32 search (qs_kernels.hip); the bf16x3
     // select kernels (kernels_bf3.hip) need option bf3_planes before the first Add
-    idx->use_qs = (cfg->compression == WV_COMPRESSION_NONE && cfg->metric != WV_METRIC_HAMMING) ? 1 : 0;
+    idx->use_qs = (cfg->compression == WV_COMPRESSION_NONE && metric_bilinear(cfg->metric)) ? 1 : 0;
     idx->kernel_opt = 0;  // auto: the block-key path (7) when the planes exist, else the legacy select kernels
     if (cfg->compression == WV_COMPRESSION_RQ8) idx->rq_bits = 8;
     if (cfg->compression == WV_COMPRESSION_RQ1) idx->rq_bits = 1;
@@ -695,6 +703,11 @@ extern "C" int wv_index_set_option(wv_index* idx, const char* key, int64_t value
     if (k == "sel_filter") { idx->sel_filter = value ? 1 : 0; return WV_OK; }
     if (k == "batch_window_us") { if (value < 0 || value > 1000000) return set_err(WV_ERR_INVALID, "batch_window_us out of range"); idx->batch_window_us = value; return WV_OK; }
     if (k == "exact_multi") { idx->exact_multi = value ? 1 : 0; return WV_OK; }
+    if (k == "l1_tile") {  // manhattan all-rows kernel: -1 auto (by list length), 0 k_exact_rows, 1 k_l1_rows
+        if (value < -1 || value > 1) return set_err(WV_ERR_INVALID, "l1_tile must be -1 (auto), 0 or 1");
+        idx->l1_tile = (int)value;
+        return WV_OK;
+    }
     if (k == "gemv_wg") { if (value < 8 || value > 65536) return set_err(WV_ERR_INVALID, "gemv_wg out of range"); idx->gemv_wg = (int)value; return WV_OK; }
     if (k == "gemv_max") { if (value < 0 || value > 4096) return set_err(WV_ERR_INVALID, "gemv_max out of range"); idx->gemv_max = (int)value; return WV_OK; }
     if (k == "batch_max") { if (value < 1) return set_err(WV_ERR_INVALID, "batch_max out of range"); idx->batch_max = value; return WV_OK; }
@@ -719,7 +732,7 @@ extern "C" int wv_index_set_option(wv_index* idx, const char* key, int64_t value
     } else if (k == "qs") {
         if (idx->cap > 0 && (value != 0) != (idx->use_qs != 0))
             return set_err(WV_ERR_INVALID, "qs must be set before the first Add");
-        idx->use_qs = value ? 1 : 0;
+        idx->use_qs = (value && metric_bilinear(idx->metric)) ? 1 : 0;  // hamming, manhattan: no block keys exist
         if (idx->dims) set_dims(idx, idx->dims);
     }
     else if (k == "bq_kernel") idx->bq_kernel = (int)value;
@@ -892,6 +905,12 @@ double gamma_n(int n) {
     return n * u / (1.0 - n * u);
 }
 
+// option l1_tile = -1: manhattan lists of at least this many queries take k_l1_rows, a single query the
+// lane-per-pair k_exact_rows.  profiles/l1_tile_ab.json (1M x 128, ms per call, simple / tiled): one
+// query 0.79 / 0.84, two 1.28 / 0.84, eight 4.70 / 0.88 -- the tiled kernel pads a list to whole tiles
+// of L1_QT queries, so it costs the same from one query to eight; the simple kernel's time grows with each.
+constexpr int L1_TILE_MIN = 2;
+
 // Exact heap replay for the listed query rows (device qlist): exact-order
 // distances of every row (k_exact_rows) then the id-ordered heap replay
 // (k_replay_scan), in groups bounded by a 2 GiB distance buffer.
@@ -919,12 +938,19 @@ int run_replay(wv_index* idx, hipStream_t s, const uint32_t* valid, const float*
             const unsigned grid = (unsigned)(F * (ld / EBLK));
 #define WV_EX(M, V) k_exact_rows<M, V><<<grid, EBLK, 0, s>>>(idx->X, idx->dpad, valid, nslots, Qn, idx->dims, d_qlist + g0, F, ld, idx->rE.as<float>(), idx->rB.as<float>())
             // AVX2 order (or AVX-512 below 128 dims, the same order): 4 queries per thread
-            const bool multi = idx->metric != WV_METRIC_HAMMING && (!v5 || idx->dims < 128) && idx->exact_multi &&
+            const bool multi = metric_bilinear(idx->metric) && (!v5 || idx->dims < 128) && idx->exact_multi &&
                                (int64_t)idx->dpad * 16 <= 65536;
             const size_t lds_q = (size_t)4 * idx->dpad * sizeof(float);
             const unsigned gridm = (unsigned)(((F + 3) / 4) * (ld / EBLK));
 #define WV_EXM(M) k_exact_rows_multi<M, 4><<<gridm, EBLK, lds_q, s>>>(idx->X, idx->dpad, valid, nslots, Qn, idx->dims, d_qlist + g0, F, ld, idx->rE.as<float>(), idx->rB.as<float>())
-            if (multi) {
+            // manhattan: the register-tiled k_l1_rows (l1_kernels.hip) from L1_TILE_MIN listed queries on
+            const bool l1t = idx->metric == WV_METRIC_MANHATTAN &&
+                             (idx->l1_tile < 0 ? F >= L1_TILE_MIN : idx->l1_tile == 1);
+            if (l1t) {
+                HIPCHK(launch_l1_rows(s, idx->X, idx->dpad, valid, nslots, Qn, idx->dims, d_qlist + g0, F, ld,
+                                      idx->rE.as<float>(), idx->rB.as<float>()));
+                idx->stats.last_route = WV_ROUTE_L1_TILE;
+            } else if (multi) {
                 switch (idx->metric) {
                 case WV_METRIC_L2_SQUARED: WV_EXM(L2); break;
                 case WV_METRIC_DOT: WV_EXM(DOT); break;
@@ -935,6 +961,7 @@ int run_replay(wv_index* idx, hipStream_t s, const uint32_t* valid, const float*
             case WV_METRIC_L2_SQUARED: if (v5) WV_EX(L2, AVX512); else WV_EX(L2, AVX256); break;
             case WV_METRIC_DOT: if (v5) WV_EX(DOT, AVX512); else WV_EX(DOT, AVX256); break;
             case WV_METRIC_COSINE_DOT: if (v5) WV_EX(COSINE, AVX512); else WV_EX(COSINE, AVX256); break;
+            case WV_METRIC_MANHATTAN: WV_EX(MANHATTAN, AVX256); break;
             default: WV_EX(HAMMING, AVX256); break;
             }
 #undef WV_EX
@@ -978,7 +1005,7 @@ int prepare_queries(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t n
 // the block-key route (search_qs) serves this index and k
 static bool qs_route(const wv_index* idx, int k) {
     return (idx->qs_planes || idx->q8_only) && !idx->has_nonfinite && (idx->kernel_opt == 0 || idx->kernel_opt == 7) &&
-           !idx->force_replay && qs_R_flat(k) > 0 && idx->metric != WV_METRIC_HAMMING;
+           !idx->force_replay && qs_R_flat(k) > 0 && metric_bilinear(idx->metric);
 }
 
 // Core batch search on device queries.  Outputs [nq][kout] device arrays.
@@ -1028,7 +1055,7 @@ static int search_core(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
     }
     if (idx->pqa_valid) return set_err(WV_ERR_UNSUPPORTED, "per-query allow lists: block-key route only");
     const int KP = k + idx->margin;
-    const bool mfma_ok = KP <= 32 && idx->metric != WV_METRIC_HAMMING && !idx->force_replay;
+    const bool mfma_ok = KP <= 32 && metric_bilinear(idx->metric) && !idx->force_replay;
     idx->stats.queries += (uint64_t)nq;
     idx->stats.batches++;
 
@@ -1334,7 +1361,7 @@ static int subindex_build(wv_index* idx, hipStream_t s, const std::vector<uint32
     sb->kernel_opt = idx->kernel_opt; sb->q8_opt = idx->q8_opt; sb->q8_R = idx->q8_R; sb->q8_filter = idx->q8_filter;
     sb->q8_shape = idx->q8_shape; sb->q8_sched = idx->q8_sched; sb->exact_filter = idx->exact_filter; sb->exact_bm = idx->exact_bm; sb->q8_bm = idx->q8_bm; sb->q8_gemv = idx->q8_gemv; sb->q8_live = idx->q8_live; sb->q8_prio = idx->q8_prio; sb->sel_split_max = idx->sel_split_max; sb->q8_bm_min = idx->q8_bm_min;
     sb->exact_cap = idx->exact_cap; sb->replay_par = idx->replay_par; sb->rp_few = idx->rp_few; sb->margin = idx->margin;
-    sb->gemv_max = idx->gemv_max; sb->gemv_wg = idx->gemv_wg; sb->exact_multi = idx->exact_multi;
+    sb->gemv_max = idx->gemv_max; sb->gemv_wg = idx->gemv_wg; sb->exact_multi = idx->exact_multi; sb->l1_tile = idx->l1_tile;
     sb->force_replay = idx->force_replay; sb->qs_force_flag = idx->qs_force_flag; sb->timing = idx->timing;
     sb->hiwater = 0;
     sb->npresent = 0;
@@ -2026,6 +2053,7 @@ extern "C" int wv_distance_batch(int32_t device, int32_t metric, int32_t variant
     case WV_METRIC_DOT: if (v5) WV_DP(DOT, AVX512); else WV_DP(DOT, AVX256); break;
     case WV_METRIC_COSINE_DOT: if (v5) WV_DP(COSINE, AVX512); else WV_DP(COSINE, AVX256); break;
     case WV_METRIC_HAMMING: WV_DP(HAMMING, AVX256); break;
+    case WV_METRIC_MANHATTAN: WV_DP(MANHATTAN, AVX256); break;
     default: A.release(); B.release(); O.release(); return set_err(WV_ERR_INVALID, "unknown metric %d", metric);
     }
 #undef WV_DP

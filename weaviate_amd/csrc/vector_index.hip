@@ -45,6 +45,7 @@ static const char* metric_name(int m) {
     case WV_METRIC_L2_SQUARED: return "l2-squared";
     case WV_METRIC_DOT: return "dot";
     case WV_METRIC_COSINE_DOT: return "cosine";
+    case WV_METRIC_MANHATTAN: return "manhattan";
     default: return "hamming";
     }
 }
@@ -166,6 +167,7 @@ extern "C" int wv_index_query_distances(wv_index* idx, const float* query, int64
             case WV_METRIC_L2_SQUARED: if (v5) WV_QD(L2, AVX512); else WV_QD(L2, AVX256); break;
             case WV_METRIC_DOT: if (v5) WV_QD(DOT, AVX512); else WV_QD(DOT, AVX256); break;
             case WV_METRIC_COSINE_DOT: if (v5) WV_QD(COSINE, AVX512); else WV_QD(COSINE, AVX256); break;
+            case WV_METRIC_MANHATTAN: WV_QD(MANHATTAN, AVX256); break;
             default: WV_QD(HAMMING, AVX256); break;
             }
 #undef WV_QD

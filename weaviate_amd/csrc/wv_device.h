@@ -14,7 +14,7 @@
 namespace wv {
 namespace {  // internal linkage: each runtime unit compiles the kernels it launches
 
-enum Metric : int { L2 = 0, DOT = 1, COSINE = 2, HAMMING = 3 };
+enum Metric : int { L2 = 0, DOT = 1, COSINE = 2, HAMMING = 3, MANHATTAN = 4 };
 enum Variant : int { AVX256 = 1, AVX512 = 2 };
 
 constexpr uint32_t NO_ID = 0xFFFFFFFFu;
@@ -158,11 +158,31 @@ __device__ __forceinline__ float exact_hamming_f32(const float* q, const float* 
     return (float)cnt;
 }
 
+// L1 (distancer/manhattan.go:20-30): one fp32 accumulator advanced in element
+// order, sum = sum + |a[i] - b[i]|; the reference has no SIMD form of it.
+// q and x are 16-byte aligned; nothing past element n - 1 is read.
+__device__ __forceinline__ float exact_manhattan(const float* __restrict__ q, const float* __restrict__ x, int n) {
+    float sum = 0.f;
+    int i = 0;
+    for (; i + 4 <= n; i += 4) {
+        const float4 a = ld4(q + i);
+        const float4 b = ld4(x + i);
+        sum = sum + fabsf(a.x - b.x);
+        sum = sum + fabsf(a.y - b.y);
+        sum = sum + fabsf(a.z - b.z);
+        sum = sum + fabsf(a.w - b.w);
+    }
+    for (; i < n; i++) sum = sum + fabsf(q[i] - x[i]);
+    return sum;
+}
+
 // Provider.SingleDist with Wrap: distancer/l2.go:46, dot_product.go:68,
-// cosine_dist.go:42-55 (1 - dot, clamped at 0), hamming.go:80.
+// cosine_dist.go:42-55 (1 - dot, clamped at 0), hamming.go:80, manhattan.go:41
+// (no normalisation, no Wrap).
 template <int METRIC, int VARIANT>
 __device__ __forceinline__ float exact_dist(const float* q, const float* x, int n) {
     if (METRIC == HAMMING) return exact_hamming_f32(q, x, n);
+    if (METRIC == MANHATTAN) return exact_manhattan(q, x, n);
     float r = exact_raw<METRIC == L2 ? L2 : DOT, VARIANT>(q, x, n);
     if (METRIC == L2) return r;
     if (METRIC == DOT) return -r;
@@ -185,9 +205,10 @@ __device__ __forceinline__ float lane_xor4(float v) {  // ds_swizzle bitmask mod
 
 // True when exact_dist8 computes exact_dist<METRIC, VARIANT> for n elements:
 // the AVX2 order, and the AVX-512 order below 128 elements where both coincide.
+// Never for hamming (a count) or manhattan (one sequential accumulator).
 template <int METRIC, int VARIANT>
 __device__ __forceinline__ bool exact8_ok(int n) {
-    return METRIC != HAMMING && (VARIANT == AVX256 || n < 128);
+    return METRIC != HAMMING && METRIC != MANHATTAN && (VARIANT == AVX256 || n < 128);
 }
 
 // exact_dist8<METRIC, G>: exact_dist<METRIC, AVX256> of G rows per 8-lane

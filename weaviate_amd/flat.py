@@ -23,10 +23,11 @@ DISTANCES = {
     "dot": _lib.METRIC_DOT,
     "l2-squared": _lib.METRIC_L2,
     "hamming": _lib.METRIC_HAMMING,
+    "manhattan": _lib.METRIC_MANHATTAN,
 }
 VARIANTS = {"auto": _lib.VARIANT_AUTO, "avx256": _lib.VARIANT_AVX256, "avx512": _lib.VARIANT_AVX512}
 PROVIDER_TYPE = {_lib.METRIC_L2: "l2-squared", _lib.METRIC_DOT: "dot", _lib.METRIC_COSINE: "cosine-dot",
-                 _lib.METRIC_HAMMING: "hamming"}
+                 _lib.METRIC_HAMMING: "hamming", _lib.METRIC_MANHATTAN: "manhattan"}
 
 
 def _fptr(a: np.ndarray):
