@@ -157,7 +157,11 @@ int wv_index_search_by_vector_batch(wv_index *idx, const float *queries, int64_t
  * block-key launch over the lists' union), "pqa_keys" (default 1: int8 dot /
  * cosine keys up to 768 dims masked per query, so each query's keys cover its
  * own rows only) and "pqa_budget_mb" (per-query bitmap memory per launch,
- * default 4096). */
+ * default 4096).  A flat + BQ index shares the launch too (option "pqa_bq",
+ * default 1): the hamming block minima run once over the
+ * lists' union, each query's R-heap replay over its own bitmap, the errors
+ * those of the one-query call; 0 groups the queries by identical list, one
+ * BQ search per group (what rq, PQ and SQ indexes always do). */
 int wv_index_search_by_vector_batch_multi_allow(wv_index *idx, const float *queries, int64_t nq, int64_t d,
                                                 int32_t k, const uint64_t *allow_ids, const int64_t *allow_offsets,
                                                 const int32_t *allow_modes, uint64_t *out_ids, float *out_dists,
@@ -168,7 +172,9 @@ int wv_index_search_by_vector_batch_multi_allow(wv_index *idx, const float *quer
  * list is the doc ids i with bit (i & 31) of word allow_bits[q * words + (i >> 5)]
  * set, when allow_modes[q] == 1 (ids past words * 32 are not listed).  At
  * 1M rows a 5 % list is 125 KB as a bitmap against 400 KB of ids.  Results
- * equal wv_index_search_by_vector_batch_multi_allow over the same lists. */
+ * equal wv_index_search_by_vector_batch_multi_allow over the same lists; the
+ * same indexes share the launch (uncompressed block keys, and flat + BQ under
+ * "pqa_bq"), the bitmaps then never becoming id lists. */
 int wv_index_search_by_vector_batch_multi_allow_bitmap(wv_index *idx, const float *queries, int64_t nq, int64_t d,
                                                        int32_t k, const uint32_t *allow_bits, int64_t words,
                                                        const int32_t *allow_modes, uint64_t *out_ids,
@@ -184,7 +190,8 @@ int wv_index_search_by_vector_batch_multi_allow_bitmap(wv_index *idx, const floa
  * their own allow lists share a launch through
  * wv_index_search_by_vector_batch_multi_allow (a dense list -- over 1/64 of
  * its slot span -- travels as a slot bitmap the calling thread builds in a
- * page-locked row of its own, option "batch_rows", default 1).  Results and
+ * page-locked row of its own, option "batch_rows", default 1; on a flat + BQ
+ * index the launch is the shared one of "pqa_bq").  Results and
  * errors equal those of a one-query wv_index_search_by_vector_batch.
  * out_ids/out_dists capacity k. */
 int wv_index_search_by_vector(wv_index *idx, const float *query, int64_t d, int32_t k, const uint64_t *allow_ids,
@@ -624,7 +631,10 @@ int wv_index_debug_bqmin(wv_index *idx, int64_t q, float *mins, int64_t *nblk, i
  * 0 = k_pq_adc2), "bq_kernel" (1 = generic BQ kernels), "timing" (1 = record
  * kernel times with HIP events), "batch_window_us" / "batch_max"
  * (micro-batcher, see wv_index_search_by_vector), "cache" (BQ.Cache /
- * RQ.Cache, default 0: see wv_index_query_distances) */
+ * RQ.Cache, default 0: see wv_index_query_distances), "pqa" / "pqa_keys" /
+ * "pqa_budget_mb" and "pqa_bq" (1 = a flat + BQ index serves per-query allow
+ * lists in one shared launch, default; 0 = grouped by list): see
+ * wv_index_search_by_vector_batch_multi_allow */
 int wv_index_set_option(wv_index *idx, const char *key, int64_t value);
 
 /* ---- LSM on-disk format: restore from flat's vectors bucket ----------------

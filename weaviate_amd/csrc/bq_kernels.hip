@@ -176,7 +176,16 @@ __global__ __launch_bounds__(256, 2) void k_bq_blockmin_lds(const uint64_t* __re
 // (lane = row, lanes 32-63 take the next visitable block speculatively: its
 // rows are offered only after the first block's, each against the heap top
 // of that moment, so the insertions are the in-order ones)
-template <int NW, bool REC, int BLK = BQBLK>
+// PQA: per-query allow bitmaps (a multi-allow batch): `valid`
+// holds one bitmap of vq words per batch query and the listed query
+// qlist[li] reads valid + qlist[li] * vq, while bmin came from the union of the
+// bitmaps -- a lower bound of the query's own block minimum, so a skipped block
+// holds no row the heap would take and a visited block offers only the
+// query's own rows, in id order.  A block without an own row counts as +inf
+// (its own valid words are its occupancy), so a sparse list inside a dense
+// union does not walk every block of the union while its heap is short.
+// A template parameter: the other instantiations compile as before.
+template <int NW, bool REC, int BLK = BQBLK, bool PQA = false>
 __global__ __launch_bounds__(64) void k_bq_replay(const uint64_t* __restrict__ codes, int64_t ccap, int words,
                                                   const uint32_t* __restrict__ valid, int64_t nslots,
                                                   const uint64_t* __restrict__ qcodes, int64_t ldq,
@@ -187,7 +196,7 @@ __global__ __launch_bounds__(64) void k_bq_replay(const uint64_t* __restrict__ c
                                                   int pop, uint64_t* __restrict__ out_ids, float* __restrict__ out_d,
                                                   int32_t* __restrict__ out_n, uint64_t* __restrict__ rec_ids,
                                                   float* __restrict__ rec_d, int32_t* __restrict__ rec_n, int cap,
-                                                  const int32_t* __restrict__ skip) {
+                                                  const int32_t* __restrict__ skip, int64_t vq) {
     // dynamic LDS: [R] heap records (PHeap) | [64] f32 | len
     extern __shared__ __attribute__((aligned(16))) unsigned char rsm[];
     HeapRec* hr = reinterpret_cast<HeapRec*>(rsm);
@@ -199,6 +208,7 @@ __global__ __launch_bounds__(64) void k_bq_replay(const uint64_t* __restrict__ c
     if (skip && skip[li]) return;  // answered by k_bq_fast
     const uint64_t* qc = qcodes + qlist[li];  // word w at qc[w * ldq]
     const float* Bq = bmin + (int64_t)li * nblk;
+    if constexpr (PQA) valid += (int64_t)qlist[li] * vq;  // the query's own bitmap from here on
     // heap state handed over by the previous shard (layout order), or empty
     const int len0 = in_len ? in_len[li] : 0;
     for (int i = lane; i < len0; i += 64) hr[i] = hr_make(in_ids[(int64_t)li * R + i], in_d[(int64_t)li * R + i]);
@@ -225,7 +235,8 @@ __global__ __launch_bounds__(64) void k_bq_replay(const uint64_t* __restrict__ c
 #pragma unroll
             for (int u = 0; u < 16; u++) {
                 const int64_t b = base + u * 64 + lane;
-                dst[u] = b < nblk ? Bq[b] : __builtin_inff();
+                if constexpr (PQA) dst[u] = (b < nblk && valid[b] != 0u) ? Bq[b] : __builtin_inff();
+                else dst[u] = b < nblk ? Bq[b] : __builtin_inff();
             }
         };
         auto win_mask = [&]() -> uint32_t {
@@ -338,7 +349,14 @@ __global__ __launch_bounds__(64) void k_bq_replay(const uint64_t* __restrict__ c
         }
     } else
     for (int64_t b0 = 0; b0 < nblk; b0 += 64) {
-        const float bm = (b0 + lane < nblk) ? Bq[b0 + lane] : __builtin_inff();
+        float bm = (b0 + lane < nblk) ? Bq[b0 + lane] : __builtin_inff();
+        if constexpr (PQA) {  // the block's 8 own valid words (vq is a multiple of 8: 32-byte aligned)
+            if (b0 + lane < nblk) {
+                const uint4* vp = reinterpret_cast<const uint4*>(valid + (b0 + lane) * (BQBLK / 32));
+                const uint4 v0 = vp[0], v1 = vp[1];
+                if ((v0.x | v0.y | v0.z | v0.w | v1.x | v1.y | v1.z | v1.w) == 0u) bm = __builtin_inff();
+            }
+        }
         int len = *s_len;
         float top = len > 0 ? hr[0].d : 0.f;
         uint64_t bmask = __ballot((b0 + lane < nblk) && bm != __builtin_inff() && (len < R || top > bm));

@@ -161,11 +161,14 @@ static int bq_blockmin(wv_index* idx, hipStream_t s, const uint32_t* valid, int6
 // heap states in_* (NULL = empty) [F][R]; pop = 1 writes the popped
 // candidates (pop order), 0 the heap states.  Ids are global (id_base + slot).
 // rec_*: record every insertion ([F][cap], count cap + 1 = overflow); out_n
-// may then be NULL (no state written).
+// may then be NULL (no state written).  vq > 0: a multi-allow batch -- valid
+// holds one bitmap of vq words per batch query (k_bq_replay<..., PQA>) and the
+// minima came from their union; such a batch keeps no record.
 static int bq_replay(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_t g0, int F, const uint64_t* in_ids,
                      const float* in_d, const int32_t* in_len, int pop, uint64_t* out_ids, float* out_d,
                      int32_t* out_n, uint64_t* rec_ids = nullptr, float* rec_d = nullptr, int32_t* rec_n = nullptr,
-                     int cap = 0, const int32_t* skip = nullptr) {
+                     int cap = 0, const int32_t* skip = nullptr, int64_t vq = 0) {
+    if (vq > 0 && rec_n) return set_err(WV_ERR_INVALID, "bq_replay: no record with per-query bitmaps");
     const int64_t nq = idx->bq_nq;
     const int R = idx->bq_R;
     const int64_t nslots = idx->hiwater;
@@ -178,26 +181,30 @@ static int bq_replay(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_
     const float* bm = idx->bqmin.as<float>();
     const size_t lds_r = packed_replay_lds(R);
     if (lds_r > 160 * 1024) return set_err(WV_ERR_UNSUPPORTED, "rescore limit %d too large for the replay heap", R);
-#define WV_RPB(NWV, RECV, BLKV)                                                                                 \
+#define WV_RPB(NWV, RECV, BLKV, PQV)                                                                            \
     do {                                                                                                        \
         if (lds_r > 64 * 1024)                                                                                  \
-            HIPCHK(hipFuncSetAttribute((const void*)k_bq_replay<NWV, RECV, BLKV>,                               \
+            HIPCHK(hipFuncSetAttribute((const void*)k_bq_replay<NWV, RECV, BLKV, PQV>,                          \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));                \
-        k_bq_replay<NWV, RECV, BLKV><<<(unsigned)F, 64, lds_r, s>>>(idx->codes, idx->cap, words, valid, nslots, qc, nq, \
-                                                              qlist + g0, F, bm, nblk, R, idx->id_base, in_ids, \
-                                                              in_d, in_len, pop, out_ids, out_d, out_n, rec_ids, \
-                                                              rec_d, rec_n, cap, skip);                         \
+        k_bq_replay<NWV, RECV, BLKV, PQV><<<(unsigned)F, 64, lds_r, s>>>(                                       \
+            idx->codes, idx->cap, words, valid, nslots, qc, nq, qlist + g0, F, bm, nblk, R, idx->id_base, in_ids, \
+            in_d, in_len, pop, out_ids, out_d, out_n, rec_ids, rec_d, rec_n, cap, skip, vq);                    \
     } while (0)
-#define WV_RPR(NWV, RECV)                                          \
+#define WV_RPR(NWV, RECV, PQV)                                     \
     do {                                                           \
         if constexpr (NWV > 0) {                                   \
-            if (b32) WV_RPB(NWV, RECV, 32);                        \
-            else WV_RPB(NWV, RECV, BQBLK);                         \
+            if (b32) WV_RPB(NWV, RECV, 32, PQV);                   \
+            else WV_RPB(NWV, RECV, BQBLK, PQV);                    \
         } else {                                                   \
-            WV_RPB(NWV, RECV, BQBLK);                              \
+            WV_RPB(NWV, RECV, BQBLK, PQV);                         \
         }                                                          \
     } while (0)
-#define WV_RP(NWV) do { if (rec_n) WV_RPR(NWV, true); else WV_RPR(NWV, false); } while (0)
+#define WV_RP(NWV)                                 \
+    do {                                           \
+        if (rec_n) WV_RPR(NWV, true, false);       \
+        else if (vq > 0) WV_RPR(NWV, false, true); \
+        else WV_RPR(NWV, false, false);            \
+    } while (0)
     switch (nw) {
     case 2: WV_RP(2); break;
     case 4: WV_RP(4); break;
@@ -294,6 +301,12 @@ int search_bq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
     int64_t G = 0;
     int rc = bq_begin(idx, s, d_qraw, nq, qd, k, &R, &G);
     if (rc) return rc;
+    // a multi-allow batch (pqa_run): valid is the union of the
+    // queries' bitmaps -- the minima run over it once -- and each query's
+    // replay reads its own bitmap pqa_valid + q * pqa_vq.  k_bq_fast finds its
+    // rows from one shared bitmap, so such a batch goes through the replay.
+    const uint32_t* own = idx->pqa_valid;
+    const int64_t own_vq = own ? idx->pqa_vq : 0;
     HIPCHK(idx->ascI.ensure((size_t)nq * R * sizeof(uint64_t)));
     HIPCHK(idx->ascD.ensure((size_t)nq * R * sizeof(float)));
     HIPCHK(idx->cn.ensure((size_t)nq * sizeof(int32_t)));
@@ -307,12 +320,12 @@ int search_bq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
         if (rc) return rc;
         HIPCHK(idx->bqSkip.ensure((size_t)nq * sizeof(int32_t)));
         int32_t* skip = idx->bqSkip.as<int32_t>() + g0;
-        const bool fast = bq_fast(idx, s, valid, g0, F, k, idx->ascI.as<uint64_t>() + g0 * R,
-                                  idx->cn.as<int32_t>() + g0, skip, &rc);
+        const bool fast = !own && bq_fast(idx, s, valid, g0, F, k, idx->ascI.as<uint64_t>() + g0 * R,
+                                          idx->cn.as<int32_t>() + g0, skip, &rc);
         if (rc) return rc;
-        rc = bq_replay(idx, s, valid, g0, F, nullptr, nullptr, nullptr, 1, idx->ascI.as<uint64_t>() + g0 * R,
-                       idx->ascD.as<float>() + g0 * R, idx->cn.as<int32_t>() + g0, nullptr, nullptr, nullptr, 0,
-                       fast ? skip : nullptr);
+        rc = bq_replay(idx, s, own ? own : valid, g0, F, nullptr, nullptr, nullptr, 1,
+                       idx->ascI.as<uint64_t>() + g0 * R, idx->ascD.as<float>() + g0 * R, idx->cn.as<int32_t>() + g0,
+                       nullptr, nullptr, nullptr, 0, fast ? skip : nullptr, own_vq);
         if (rc) return rc;
     }
     rc = bq_rescore(idx, s, idx->ascI.as<uint64_t>(), idx->cn.as<int32_t>(), idx->candE.as<float>());

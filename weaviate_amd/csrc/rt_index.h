@@ -281,6 +281,7 @@ struct wv_index {
     int64_t pqa_split_max = 64;
     int pqa_alone = 1;
     int pqa_keys = 1;       // option pqa_keys: per-query masked int8 keys (k_q8_blockkey<.., MASK>)
+    int pqa_bq = 1;         // option pqa_bq: a BQ index shares the launch too (search_bq: union minima, own replays)
     std::atomic<int> batch_rows{1};  // option batch_rows: the batcher's dense lists as slot bitmaps (read by callers)
     int64_t pqa_vq = 0;
     int64_t cur_vq = 0;

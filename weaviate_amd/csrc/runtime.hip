@@ -789,6 +789,7 @@ extern "C" int wv_index_set_option(wv_index* idx, const char* key, int64_t value
     else if (k == "sel_lower") idx->sel_lower = value ? 1 : 0;  // per-query allow lists share one block-key launch
     else if (k == "pqa_alone") idx->pqa_alone = value ? 1 : 0;  // unresolved per-query lists searched alone
     else if (k == "pqa_keys") idx->pqa_keys = value ? 1 : 0;    // per-query masked int8 keys
+    else if (k == "pqa_bq") idx->pqa_bq = value ? 1 : 0;        // BQ: per-query allow lists share one launch
     else if (k == "bq_fast") idx->bq_fast = value ? 1 : 0;  // replay-free BQ answers when ties cannot matter
     else if (k == "rp_few") idx->rp_few = value;  // replay lists up to this long (device-counted) take the one-launch form
     else if (k == "batch_rows") idx->batch_rows = value ? 1 : 0;  // batcher: dense lists as slot bitmaps
@@ -1531,6 +1532,19 @@ static int multi_allow_grouped(wv_index* idx, const float* queries, int64_t nq, 
     return WV_OK;
 }
 
+// the indexes whose multi-allow batch shares one launch: the uncompressed
+// block-key route (search_qs) and, under option pqa_bq, flat + BQ (search_bq:
+// the block minima over the union, each query's R-heap replay over its own
+// bitmap).  rq, PQ and SQ stay grouped by list.
+static bool pqa_bq_route(const wv_index* idx) {
+    return idx->compression == WV_COMPRESSION_BQ && idx->pqa_bq && !idx->rq_bits;
+}
+static bool pqa_shared(const wv_index* idx, int64_t nq, int64_t d, int32_t k) {
+    if (!idx->pqa || nq <= 1 || idx->dims == 0 || d != idx->dims || k <= 0 || idx->npresent <= 0) return false;
+    if (pqa_bq_route(idx)) return true;
+    return idx->compression == WV_COMPRESSION_NONE && !idx->rq_bits && qs_route(idx, k);
+}
+
 // the select's threshold depth per query (k_blk_select mq): a block key is
 // the minimum over the union's rows, this query's own with probability ~ its
 // share rho of the union, so ~ (k+1) / rho blocks hold its k+1 nearest; twice
@@ -1570,7 +1584,8 @@ static int pqa_run(wv_index* idx, hipStream_t s, const float* queries, int64_t n
     // instead of by the one-wave replay inside the launch, which walks every
     // block key of the union for one query (35 ms at 1M rows, 2 % lists)
     HIPCHK(idx->oF.ensure((size_t)nq * sizeof(int32_t)));
-    int32_t* dflags = idx->pqa_alone ? idx->oF.as<int32_t>() : nullptr;
+    // (search_bq resolves every query itself and writes no flags)
+    int32_t* dflags = idx->pqa_alone && !pqa_bq_route(idx) ? idx->oF.as<int32_t>() : nullptr;
     int rc = search_core(idx, s, idx->qraw.as<float>(), nq, d, k, 0, uni, idx->npresent, idx->oIds.as<uint64_t>(),
                          idx->oD.as<float>(), idx->oN.as<int32_t>(), dflags);
     idx->pqa_valid = nullptr;
@@ -1659,16 +1674,16 @@ extern "C" int wv_index_search_by_vector_batch_multi_allow(wv_index* idx, const 
     std::unique_lock<std::mutex> g(idx->mu);
     const int64_t vq = round_up(std::max<int64_t>(idx->hiwater, 1), 256) / 32;  // words per query bitmap
     const int64_t qmax = std::max<int64_t>(1, (idx->pqa_budget_mb << 20) / (vq * (int64_t)sizeof(uint32_t)));
-    const bool fast = idx->pqa && nq > 1 && idx->compression == WV_COMPRESSION_NONE && !idx->rq_bits &&
-                      idx->dims != 0 && d == idx->dims && k > 0 && idx->npresent > 0 && qs_route(idx, k);
+    const bool fast = pqa_shared(idx, nq, d, k);
+    const bool keyed = fast && !pqa_bq_route(idx);  // the block-key select's depths and split
     if (!fast) {
         g.unlock();
         return multi_allow_grouped(idx, queries, nq, d, k, allow_ids, allow_offsets, allow_modes, out_ids, out_dists,
                                    out_counts);
     }
-    std::vector<double> md;
-    pqa_depths(idx, nq, k, allow_offsets, allow_modes, md);
-    if (!t_pqa_nosplit && !pqa_keys_route(idx)) {  // (per-query keys serve sparse lists in the launch)
+    std::vector<double> md((size_t)nq, 0.0);
+    if (keyed) pqa_depths(idx, nq, k, allow_offsets, allow_modes, md);
+    if (keyed && !t_pqa_nosplit && !pqa_keys_route(idx)) {  // (per-query keys serve sparse lists in the launch)
         // lists too sparse for the union's keys (deeper than the 960-block
         // lists) would end in the one-wave replay, a walk over every block
         // key: a few of them go as their own searches instead (an allow list
@@ -1787,12 +1802,12 @@ static int pqa_bitmap_core(wv_index* idx, std::unique_lock<std::mutex>& g, const
     };
     const int64_t vq = round_up(std::max<int64_t>(idx->hiwater, 1), 256) / 32;
     const int64_t qmax = std::max<int64_t>(1, (idx->pqa_budget_mb << 20) / (vq * (int64_t)sizeof(uint32_t) * 2));
-    const bool fast = idx->pqa && nq > 1 && idx->compression == WV_COMPRESSION_NONE && !idx->rq_bits &&
-                      idx->dims != 0 && d == idx->dims && k > 0 && idx->npresent > 0 && qs_route(idx, k) && nq <= qmax;
-    std::vector<double> md;
-    if (fast) pqa_depths(idx, nq, k, off.data(), allow_modes, md);
+    const bool fast = pqa_shared(idx, nq, d, k) && nq <= qmax;
+    const bool keyed = fast && !pqa_bq_route(idx);  // the block-key select's depths and split
+    std::vector<double> md((size_t)nq, 0.0);
+    if (keyed) pqa_depths(idx, nq, k, off.data(), allow_modes, md);
     bool split = false;
-    if (fast && !pqa_keys_route(idx)) {  // the id-list call's split of too-sparse lists (see there)
+    if (keyed && !pqa_keys_route(idx)) {  // the id-list call's split of too-sparse lists (see there)
         int64_t nsp = 0;
         for (int64_t q = 0; q < nq; q++) nsp += md[(size_t)q] > 960.0;
         split = nsp > 0 && nsp <= idx->pqa_split_max && nsp < nq;
