@@ -161,7 +161,14 @@ int wv_index_search_by_vector_batch(wv_index *idx, const float *queries, int64_t
  * default 1): the hamming block minima run once over the
  * lists' union, each query's R-heap replay over its own bitmap, the errors
  * those of the one-query call; 0 groups the queries by identical list, one
- * BQ search per group (what rq, PQ and SQ indexes always do). */
+ * BQ search per group (what PQ and SQ indexes always do).  A flat rq-8 / rq-1
+ * index on the integer-MFMA route shares it as well (option "pqa_rq", default
+ * 1): the exact block minima and the candidate select run once
+ * over the lists' union, each query's candidates and -- where they do not
+ * prove its R-list -- its R-heap replay over its own bitmap; 0, the
+ * distance-matrix route ("rq_mfma" 0, rq-1 without its +-1 plane, more than
+ * 1024 rotated dims, a rescore limit past the candidate lists) and a batch
+ * whose keys pass 4 GiB run one rq search per distinct list. */
 int wv_index_search_by_vector_batch_multi_allow(wv_index *idx, const float *queries, int64_t nq, int64_t d,
                                                 int32_t k, const uint64_t *allow_ids, const int64_t *allow_offsets,
                                                 const int32_t *allow_modes, uint64_t *out_ids, float *out_dists,
@@ -173,8 +180,9 @@ int wv_index_search_by_vector_batch_multi_allow(wv_index *idx, const float *quer
  * set, when allow_modes[q] == 1 (ids past words * 32 are not listed).  At
  * 1M rows a 5 % list is 125 KB as a bitmap against 400 KB of ids.  Results
  * equal wv_index_search_by_vector_batch_multi_allow over the same lists; the
- * same indexes share the launch (uncompressed block keys, and flat + BQ under
- * "pqa_bq"), the bitmaps then never becoming id lists. */
+ * same indexes share the launch (uncompressed block keys, flat + BQ under
+ * "pqa_bq", flat rq-8 / rq-1 under "pqa_rq"), the bitmaps then never becoming
+ * id lists. */
 int wv_index_search_by_vector_batch_multi_allow_bitmap(wv_index *idx, const float *queries, int64_t nq, int64_t d,
                                                        int32_t k, const uint32_t *allow_bits, int64_t words,
                                                        const int32_t *allow_modes, uint64_t *out_ids,
@@ -191,9 +199,9 @@ int wv_index_search_by_vector_batch_multi_allow_bitmap(wv_index *idx, const floa
  * wv_index_search_by_vector_batch_multi_allow (a dense list -- over 1/64 of
  * its slot span -- travels as a slot bitmap the calling thread builds in a
  * page-locked row of its own, option "batch_rows", default 1; on a flat + BQ
- * index the launch is the shared one of "pqa_bq").  Results and
- * errors equal those of a one-query wv_index_search_by_vector_batch.
- * out_ids/out_dists capacity k. */
+ * or rq-8 / rq-1 index the launch is the shared one of "pqa_bq" / "pqa_rq").
+ * Results and errors equal those of a one-query
+ * wv_index_search_by_vector_batch.  out_ids/out_dists capacity k. */
 int wv_index_search_by_vector(wv_index *idx, const float *query, int64_t d, int32_t k, const uint64_t *allow_ids,
                               int64_t n_allow, int32_t allow_mode, uint64_t *out_ids, float *out_dists,
                               int32_t *out_count);
@@ -633,7 +641,8 @@ int wv_index_debug_bqmin(wv_index *idx, int64_t q, float *mins, int64_t *nblk, i
  * (micro-batcher, see wv_index_search_by_vector), "cache" (BQ.Cache /
  * RQ.Cache, default 0: see wv_index_query_distances), "pqa" / "pqa_keys" /
  * "pqa_budget_mb" and "pqa_bq" (1 = a flat + BQ index serves per-query allow
- * lists in one shared launch, default; 0 = grouped by list): see
+ * lists in one shared launch, default; 0 = grouped by list) and "pqa_rq" (the
+ * same for a flat rq-8 / rq-1 index on the integer-MFMA route, default 1): see
  * wv_index_search_by_vector_batch_multi_allow */
 int wv_index_set_option(wv_index *idx, const char *key, int64_t value);
 

@@ -1874,6 +1874,25 @@ static bool rq8_route(const wv_index* idx, int R) {
            qs_R(R + 1) != 0 && idx->hiwater > 0;
 }
 
+// query chunks of rq8_candidates: key rows of at most 4 GiB
+static int64_t rq8_chunk(const wv_index* idx) {
+    const int64_t nblk = (idx->hiwater + 31) / 32;
+    return std::max<int64_t>(256, ((4ll << 30) / (nblk * 4)) / 256 * 256);
+}
+// every query's keys of a batch of nq stay in qsKey (rq8_replay_list reads them)
+static bool rq8_one_chunk(const wv_index* idx, int64_t nq) { return round_up(nq, 256) <= rq8_chunk(idx); }
+
+// a multi-allow batch of nq queries shares one search_rq: the
+// integer-MFMA route, and every query's keys kept (one query chunk), since the
+// replay of the unproven queries reads them (k_rq8_replay<.., PQA>; the
+// distance-matrix replay has no per-query form).  Whatever search_rq would
+// refuse is left to the one-query calls, whose errors the batch then reports.
+bool rq_pqa_route(const wv_index* idx, int64_t nq, int k) {
+    if (!idx->rq_bits || !idx->rq_ready || k <= 0 || idx->rq_serial == 8) return false;
+    const int R = idx->rescore_limit > k ? idx->rescore_limit : k;
+    return R <= 8192 && rq8_route(idx, R) && rq8_one_chunk(idx, nq);
+}
+
 template <int NC>
 static void launch_rq8_keys(const RQ8Args& a, unsigned grid, hipStream_t s, int bits) {
     constexpr size_t lds = (size_t)rq8_nbuf(NC) * ((size_t)32 * 64 * NC + 656);  // the ring (k_rq8_keys)
@@ -1890,16 +1909,21 @@ static void launch_rq8_keys(const RQ8Args& a, unsigned grid, hipStream_t s, int 
 
 // exact rq-8 block minima -> candidate blocks -> exact distances of their
 // rows: the ascending R-lists (ascI / ascD / ascN) of every query, oF[q] = 1
-// where a tie or a NaN leaves the heap's order to the replay
-static int rq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const uint32_t* valid) {
+// where a tie or a NaN leaves the heap's order to the replay.  own != NULL: a
+// multi-allow batch -- valid is the union of the queries' bitmaps (the keys
+// and the select run over it once), own holds one bitmap of own_vq words per
+// query for the candidates' rows (k_rq8_cand<.., PQA>), and oF[q] = 1 as well
+// where the query's own candidates do not prove its R-list.
+static int rq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const uint32_t* valid,
+                          const uint32_t* own = nullptr, int64_t own_vq = 0) {
     const int D = idx->rq_D, NC = D / 64;
     const int64_t nblk = (idx->hiwater + 31) / 32;
     const int RT = qs_R(R + 1);
     const int Lc = 64 * (RT - 1);
     const int64_t nq_pad = round_up(nq, 256);
-    // query chunks: key rows of at most 4 GiB
-    int64_t QC = std::max<int64_t>(256, ((4ll << 30) / (nblk * 4)) / 256 * 256);
-    QC = std::min<int64_t>(QC, nq_pad);
+    const int64_t QC = std::min<int64_t>(rq8_chunk(idx), nq_pad);
+    if (own && !rq8_one_chunk(idx, nq)) return set_err(WV_ERR_UNSUPPORTED, "rq: per-query allow lists need one query chunk");
+    if (own) HIPCHK(idx->rq8M.ensure((size_t)nq * sizeof(float)));
     HIPCHK(idx->rq8Qp.ensure((size_t)nq_pad * D));
     HIPCHK(idx->rq8Qcs.ensure((size_t)nq_pad * sizeof(uint32_t)));
     HIPCHK(idx->rq8Qm.ensure((size_t)nq_pad * sizeof(float4)));
@@ -1977,22 +2001,30 @@ static int rq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const
         int32_t* of = idx->oF.as<int32_t>() + c0;
         const size_t lq = (size_t)4 * (bits == 8 ? D : (5 * (D / 64) + 1) / 2 * 16);
         const void* qsrc = bits == 8 ? (const void*)a.Qp : idx->rqq.p;
-#define WV_RQC(RTV, B)                                                                                                \
-    k_rq8_cand<RTV, B><<<gw, 256, lq, s>>>(idx->rq_codes, idx->cap, idx->rq_meta, valid, idx->hiwater, qsrc, c0,       \
-                                           a.qmeta, D, fl2, fcos, cand, Lc, ncand, (int)cn, R, idx->id_base,           \
-                                           idx->ascI.as<uint64_t>() + c0 * R, idx->ascD.as<float>() + c0 * R,         \
-                                           idx->ascN.as<int32_t>() + c0, of)
-#define WV_RQ8(RTV)                                                                                                   \
+        float* mq = own ? idx->rq8M.as<float>() + c0 : nullptr;
+#define WV_RQC(RTV, B, PQV)                                                                                           \
+    k_rq8_cand<RTV, B, PQV><<<gw, 256, lq, s>>>(idx->rq_codes, idx->cap, idx->rq_meta, PQV ? own : valid,              \
+                                                idx->hiwater, qsrc, c0, a.qmeta, D, fl2, fcos, cand, Lc, ncand,      \
+                                                (int)cn, R, idx->id_base, idx->ascI.as<uint64_t>() + c0 * R,         \
+                                                idx->ascD.as<float>() + c0 * R, idx->ascN.as<int32_t>() + c0, of,    \
+                                                own_vq, mq)
+#define WV_RQP(RTV, PQV)                                                                                              \
     do {                                                                                                              \
-        k_rq8_sel<RTV><<<gw, 256, 0, s>>>(a.key, nblk, nblk, (int)cn, R, cand, Lc, ncand, of);                        \
-        if (bits == 8) WV_RQC(RTV, 8);                                                                                 \
-        else WV_RQC(RTV, 1);                                                                                           \
+        k_rq8_sel<RTV, PQV><<<gw, 256, 0, s>>>(a.key, nblk, nblk, (int)cn, R, cand, Lc, ncand, of, mq);               \
+        if (bits == 8) WV_RQC(RTV, 8, PQV);                                                                            \
+        else WV_RQC(RTV, 1, PQV);                                                                                      \
+    } while (0)
+#define WV_RQ8(RTV)                  \
+    do {                             \
+        if (own) WV_RQP(RTV, true);  \
+        else WV_RQP(RTV, false);     \
     } while (0)
         if (RT == 2) WV_RQ8(2);
         else if (RT == 4) WV_RQ8(4);
         else if (RT == 8) WV_RQ8(8);
         else WV_RQ8(16);
 #undef WV_RQ8
+#undef WV_RQP
 #undef WV_RQC
         HIPCHK(hipGetLastError());
     }
@@ -2085,10 +2117,16 @@ static int rq_replay(wv_index* idx, hipStream_t s, const uint32_t* valid, int R,
 
 // the listed queries' R-heaps replayed from the MFMA route's exact 32-row
 // minima (k_rq8_replay), when the last rq8_candidates kept every query's keys
-// (one query chunk); else the distance-matrix replay (rq_replay)
+// (one query chunk); else the distance-matrix replay (rq_replay).  vq > 0: a
+// multi-allow batch -- valid holds one bitmap of vq words per batch query
+// (k_rq8_replay<.., PQA>), the keys came from their union, and there is no
+// distance-matrix form (rq_pqa_route admits only what stays here).
 static int rq8_replay_list(wv_index* idx, hipStream_t s, const uint32_t* valid, int R, const int32_t* list,
-                           int64_t n, int64_t nq) {
-    if (idx->rq_dbg_nq != nq || idx->rq_serial == 8) return rq_replay(idx, s, valid, R, list, n);
+                           int64_t n, int64_t nq, int64_t vq = 0) {
+    if (idx->rq_dbg_nq != nq || idx->rq_serial == 8) {
+        if (vq > 0) return set_err(WV_ERR_UNSUPPORTED, "rq: per-query allow lists need the key replay");
+        return rq_replay(idx, s, valid, R, list, n);
+    }
     idx->stats.replayed_queries += (uint64_t)n;
     const int D = idx->rq_D;
     const int64_t nblk = idx->rq_dbg_nb;
@@ -2096,17 +2134,23 @@ static int rq8_replay_list(wv_index* idx, hipStream_t s, const uint32_t* valid, 
     const float fcos = idx->metric == WV_METRIC_COSINE_DOT ? 1.f : 0.f;
     const size_t lds = rq8_replay_lds(R, rq_query_lds_u4(idx->rq_bits, D));
     const bool b8 = idx->rq_bits == 8;
-    const void* fn = b8 ? (const void*)k_rq8_replay<8> : (const void*)k_rq8_replay<1>;
+    const void* fn = vq > 0 ? (b8 ? (const void*)k_rq8_replay<8, true> : (const void*)k_rq8_replay<1, true>)
+                            : (b8 ? (const void*)k_rq8_replay<8> : (const void*)k_rq8_replay<1>);
     if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const void* qsrc = b8 ? (const void*)idx->rq8Qp.p : idx->rqq.p;
-#define WV_RQR(B)                                                                                                  \
-    k_rq8_replay<B><<<(unsigned)n, 512, lds, s>>>(idx->qsKey.as<float>(), nblk, nblk, idx->rq_codes, idx->cap,      \
-                                                 idx->rq_meta, valid, idx->hiwater, qsrc, 0, idx->rq8Qm.as<float4>(), \
-                                                 D, fl2, fcos, list, (int)n, R, idx->id_base,                      \
-                                                 idx->ascI.as<uint64_t>(), idx->ascD.as<float>(),                  \
-                                                 idx->ascN.as<int32_t>())
-    if (b8) WV_RQR(8);
-    else WV_RQR(1);
+#define WV_RQR(B, PQV)                                                                                             \
+    k_rq8_replay<B, PQV><<<(unsigned)n, 512, lds, s>>>(idx->qsKey.as<float>(), nblk, nblk, idx->rq_codes, idx->cap, \
+                                                      idx->rq_meta, valid, idx->hiwater, qsrc, 0,                  \
+                                                      idx->rq8Qm.as<float4>(), D, fl2, fcos, list, (int)n, R,      \
+                                                      idx->id_base, idx->ascI.as<uint64_t>(),                      \
+                                                      idx->ascD.as<float>(), idx->ascN.as<int32_t>(), vq)
+    if (vq > 0) {
+        if (b8) WV_RQR(8, true);
+        else WV_RQR(1, true);
+    } else {
+        if (b8) WV_RQR(8, false);
+        else WV_RQR(1, false);
+    }
 #undef WV_RQR
     HIPCHK(hipGetLastError());
     return WV_OK;
@@ -2146,6 +2190,17 @@ int search_rq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
     HIPCHK(idx->ascN.ensure((size_t)nq * sizeof(int32_t)));
     HIPCHK(idx->candE.ensure((size_t)nq * R * sizeof(float)));
     const bool mfma = rq8_route(idx, R);
+    // a multi-allow batch (pqa_run): valid is the union of the
+    // queries' bitmaps -- the keys and the select run over it once -- and each
+    // query's candidates and replay read its own bitmap pqa_valid + q * pqa_vq
+    const uint32_t* own = idx->pqa_valid;
+    const int64_t own_vq = own ? idx->pqa_vq : 0;
+    // rq_pqa_route is the one rule: the gate (pqa_shared) asked it under the same
+    // lock before it set pqa_valid, so this never fires for a caller; it holds
+    // the MFMA route and the one-chunk condition that rq8_candidates and
+    // rq8_replay_list below rely on (their own refusals are unreachable past it)
+    if (own && !rq_pqa_route(idx, nq, k))
+        return set_err(WV_ERR_UNSUPPORTED, "rq: per-query allow lists outside the shared route");
     idx->bq_nq = nq;
     idx->bq_R = R;
     if (!mfma) {
@@ -2154,7 +2209,7 @@ int search_rq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
         rc = bq_rescore(idx, s, idx->ascI.as<uint64_t>(), idx->ascN.as<int32_t>(), idx->candE.as<float>());
         if (rc) return rc;
     } else {
-        rc = rq8_candidates(idx, s, nq, R, valid);
+        rc = rq8_candidates(idx, s, nq, R, valid, own, own_vq);
         if (rc) return rc;
         idx->stats.last_group_queries = (uint64_t)nq;
         // oF: 1 = replayed, 2 = decided by the rescored distances (k_rq_tiecheck:
@@ -2175,7 +2230,7 @@ int search_rq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
         HIPCHK(hipMemcpyAsync(cnt, idx->flCtr.p, sizeof(cnt), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (cnt[1] > 0) {
-            rc = rq8_replay_list(idx, s, valid, R, list, cnt[1], nq);
+            rc = rq8_replay_list(idx, s, own ? own : valid, R, list, cnt[1], nq, own_vq);
             if (rc) return rc;
             const int64_t np = (int64_t)cnt[1] * R;
             const bool v5 = idx->variant == WV_VARIANT_AVX512;

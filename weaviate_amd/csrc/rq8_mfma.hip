@@ -450,11 +450,14 @@ __global__ __launch_bounds__(512, 2) void k_rq8_keys(RQ8Args a) {
 // smallest block minima (WaveTopL), M = the (R+1)-th; cand[q] = the blocks with
 // minimum <= M (a sorted prefix of the list).  oflag[q] = 1 when the list's
 // last entry is still <= M (ties at M may run past it): the query is replayed.
+// PQA (a multi-allow batch): the keys are minima over the union
+// of the batch's lists; the selection is the same and mout[q] = M goes to
+// k_rq8_cand<.., PQA>, whose proof needs it.
 // ---------------------------------------------------------------------------
-template <int RT>
+template <int RT, bool PQA = false>
 __global__ __launch_bounds__(256) void k_rq8_sel(const float* __restrict__ key, int64_t ldk, int64_t nb, int nq, int R,
                                                  uint32_t* __restrict__ cand, int Lc, int32_t* __restrict__ ncand,
-                                                 int32_t* __restrict__ oflag) {
+                                                 int32_t* __restrict__ oflag, float* __restrict__ mout) {
     constexpr int U = 16;
     __shared__ float sbk[4][64];
     __shared__ uint32_t sbi[4][64];
@@ -495,6 +498,7 @@ __global__ __launch_bounds__(256) void k_rq8_sel(const float* __restrict__ key, 
     if (lane == 0) {
         ncand[q] = cnt < Lc ? cnt : Lc;
         oflag[q] = last_in ? 1 : 0;
+        if constexpr (PQA) mout[q] = M;
     }
 }
 
@@ -595,7 +599,17 @@ __host__ __device__ constexpr int rq_query_lds_u4(int bits, int D) { return bits
 // BITS = 1: rq-1's exact distance as k_rq1_dist computes it (xor + popcount of
 // the word-major bit codes against the 5 query planes, copied to LDS from
 // the group-tiled layout; query q of this launch is q_base + q there).
-template <int RT, int BITS>
+// PQA: per-query allow bitmaps (a multi-allow batch): `valid`
+// holds one bitmap of vq words per batch query and query q_base + q offers
+// only the rows of its own, while the candidate blocks came from keys over
+// the union of the bitmaps (threshold M = mq[q], k_rq8_sel<.., PQA>).  R + 1
+// union keys <= M no longer mean R + 1 own rows <= M, so the R-list is
+// written only when the (R+1)-th smallest own candidate distance exists and is
+// <= M: every own row outside the candidate blocks is >= its block's union
+// key > M, hence past the R smallest.  Else oflag[q] = 1 (always so for a
+// list of at most R rows).  A template parameter: the other instantiations
+// compile as before.
+template <int RT, int BITS, bool PQA = false>
 __global__ __launch_bounds__(256) void k_rq8_cand(const void* __restrict__ codes_, int64_t cap,
                                                   const float4* __restrict__ meta, const uint32_t* __restrict__ valid,
                                                   int64_t nslots, const void* __restrict__ qsrc, int64_t q_base,
@@ -603,7 +617,8 @@ __global__ __launch_bounds__(256) void k_rq8_cand(const void* __restrict__ codes
                                                   const uint32_t* __restrict__ cand, int Lc,
                                                   const int32_t* __restrict__ ncand, int nq, int R, uint64_t id_base,
                                                   uint64_t* __restrict__ ascI, float* __restrict__ ascD,
-                                                  int32_t* __restrict__ ascN, int32_t* __restrict__ oflag) {
+                                                  int32_t* __restrict__ ascN, int32_t* __restrict__ oflag, int64_t vq,
+                                                  const float* __restrict__ mq) {
     // [4][D / 16] query code bytes (rq-8) or [4][5 W] planes (rq-1)
     extern __shared__ __attribute__((aligned(16))) uint4 cqs[];
     __shared__ float sbk[4][64];
@@ -621,6 +636,7 @@ __global__ __launch_bounds__(256) void k_rq8_cand(const void* __restrict__ codes
     wave_sync_lds();
     const float4 ym = qmeta[q];
     const int nc = ncand[q];
+    if constexpr (PQA) valid += (q_base + q) * vq;  // the query's own bitmap from here on
     WaveTopL<RT> t;
     t.init();
     int nvalid = 0;
@@ -630,7 +646,9 @@ __global__ __launch_bounds__(256) void k_rq8_cand(const void* __restrict__ codes
         const bool has = bi < nc;
         const uint32_t blk = has ? cand[(int64_t)q * Lc + bi] : 0u;
         const int64_t slot = (int64_t)blk * 32 + (lane & 31);
-        const bool ok = has && slot < nslots && ((valid[blk] >> (lane & 31)) & 1u);
+        bool ok = has && slot < nslots;
+        if constexpr (PQA) ok = ok && (int64_t)blk < vq;  // (vq >= the block count: a bitmap is never shorter)
+        ok = ok && ((valid[blk] >> (lane & 31)) & 1u);
         float dist = __builtin_inff();
         if (ok) {
             dist = rq_row_dist<BITS>(codes_, cap, meta, slot, qs, ym, D, fl2, fcos);
@@ -657,7 +675,12 @@ __global__ __launch_bounds__(256) void k_rq8_cand(const void* __restrict__ codes
         tie_b = tie_b || (eq && e + 1 == R);
         tie_i = tie_i || (eq && e + 1 < R);
     }
-    if (__any(tie_b) || __any(nan)) {
+    bool unproven = false;
+    if constexpr (PQA) {  // the (R+1)-th smallest own candidate: there, finite and within the union threshold
+        const float kr = t.key_at(R);
+        unproven = !(nvalid > R && kr <= mq[q] && kr < __builtin_inff());
+    }
+    if (__any(tie_b) || __any(nan) || unproven) {
         if (lane == 0) {
             oflag[q] = 1;
             ascN[q] = 0;
@@ -726,12 +749,20 @@ __global__ __launch_bounds__(256) void k_rq_tiecheck(const float* __restrict__ c
 // passes a window whose minimum cannot beat a full heap's top without
 // touching its keys (the test is the per-block one applied to the window's
 // smallest key: no block of it would be a candidate).
+// PQA: per-query allow bitmaps (a multi-allow batch): `valid`
+// holds one bitmap of vq words per batch query and query q_base + q reads its
+// own, while the keys (and so the window minima) are minima over the union of
+// the bitmaps -- lower bounds of the query's own block minima.  A skipped
+// block has union minimum >= top, so no own row of it could pass; a visited
+// block offers only own rows, in id order.  A block whose own word is 0 is not
+// a candidate even while the heap is short, so a sparse list inside a dense
+// union does not recompute every block of the union.
 // ---------------------------------------------------------------------------
 constexpr int RQ_RP_WMAX = 4096;  // windows with an LDS minimum (2M blocks, 67M rows)
 __host__ __device__ constexpr size_t rq8_replay_lds(int R, int qu4) {
     return (size_t)R * 16 + 16 + (size_t)qu4 * 16 + 512 * 4 + 16 * 32 * 4 + 16 * 4 + 8 * 4 + RQ_RP_WMAX * 4;
 }
-template <int BITS>
+template <int BITS, bool PQA = false>
 __global__ __launch_bounds__(512) void k_rq8_replay(const float* __restrict__ key, int64_t ldk, int64_t nblk,
                                                     const void* __restrict__ codes, int64_t cap,
                                                     const float4* __restrict__ meta, const uint32_t* __restrict__ valid,
@@ -739,7 +770,7 @@ __global__ __launch_bounds__(512) void k_rq8_replay(const float* __restrict__ ke
                                                     const float4* __restrict__ qmeta, int D, float fl2, float fcos,
                                                     const int32_t* __restrict__ list, int nlist, int R,
                                                     uint64_t id_base, uint64_t* __restrict__ ascI,
-                                                    float* __restrict__ ascD, int32_t* __restrict__ ascN) {
+                                                    float* __restrict__ ascD, int32_t* __restrict__ ascN, int64_t vq) {
     extern __shared__ __attribute__((aligned(16))) unsigned char rsm[];
     HeapRec* hr = reinterpret_cast<HeapRec*>(rsm);
     int* s_len = reinterpret_cast<int*>(hr + R);
@@ -757,6 +788,7 @@ __global__ __launch_bounds__(512) void k_rq8_replay(const float* __restrict__ ke
     if (tid == 0) *s_len = 0;
     const float4 ym = qmeta[q];
     const float* kq = key + (int64_t)q * ldk;
+    if constexpr (PQA) valid += (q_base + q) * vq;  // the query's own bitmap from here on
     const int64_t nwin = (nblk + 511) / 512;
     const int64_t nwm = nwin < RQ_RP_WMAX ? nwin : RQ_RP_WMAX;
     for (int64_t w = wave; w < nwm; w += 8) {
@@ -777,7 +809,8 @@ __global__ __launch_bounds__(512) void k_rq8_replay(const float* __restrict__ ke
         // (uniform: every thread reads the same heap state and window minimum)
         if (w0 / 512 < nwm && len >= R && !(top > wmin[w0 / 512])) continue;
         const float kcur = w0 + tid < nblk ? kq[w0 + tid] : __builtin_inff();
-        const bool cand = w0 + tid < nblk && (len < R || top > kcur);
+        bool cand = w0 + tid < nblk && (len < R || top > kcur);
+        if constexpr (PQA) cand = cand && w0 + tid < vq && valid[w0 + tid] != 0u;  // occupancy: an own row at all
         const uint64_t mb = __ballot(cand);
         if (lane == 0) wcnt[wave] = __popcll(mb);
         __syncthreads();

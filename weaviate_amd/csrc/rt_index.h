@@ -267,6 +267,7 @@ struct wv_index {
     float* pq8_n2 = nullptr;
     DBuf pq8Max, pq8Mu, pq8Tmp, pq8Qc, qsCand2;
     DBuf rq8Qp, rq8Qcs, rq8Qm, rq8Fq, rq8Fm;                  // rq-8 MFMA route: query planes, flagged queries
+    DBuf rq8M;                                                // a multi-allow batch: the select's threshold M per query
     int rq_mfma = 1;
     // per-query allow lists (wv_index_search_by_vector_batch_allow): the exact
     // pass and the replays of search_qs read query q's bitmap at
@@ -282,6 +283,7 @@ struct wv_index {
     int pqa_alone = 1;
     int pqa_keys = 1;       // option pqa_keys: per-query masked int8 keys (k_q8_blockkey<.., MASK>)
     int pqa_bq = 1;         // option pqa_bq: a BQ index shares the launch too (search_bq: union minima, own replays)
+    int pqa_rq = 1;         // option pqa_rq: an rq-8 / rq-1 index as well (search_rq: union keys, own candidates and replays)
     std::atomic<int> batch_rows{1};  // option batch_rows: the batcher's dense lists as slot bitmaps (read by callers)
     int64_t pqa_vq = 0;
     int64_t cur_vq = 0;
@@ -411,6 +413,7 @@ int search_hnsw_flat(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t 
                      const uint32_t* valid, uint64_t* o_ids, float* o_d, int32_t* o_n);
 int pq_fit_rows(wv_index* idx, const float* dT, int64_t n, uint64_t seed);
 int64_t bq_max_batch(const wv_index* idx);
+bool rq_pqa_route(const wv_index* idx, int64_t nq, int k);
 int rq_init(wv_index* idx);
 int rq_encode_queries(wv_index* idx, hipStream_t s, int64_t nq);
 int rq_dist(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_t q0, int F, int64_t ld, float* E, float* bmin,

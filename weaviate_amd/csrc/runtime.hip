@@ -790,6 +790,7 @@ extern "C" int wv_index_set_option(wv_index* idx, const char* key, int64_t value
     else if (k == "pqa_alone") idx->pqa_alone = value ? 1 : 0;  // unresolved per-query lists searched alone
     else if (k == "pqa_keys") idx->pqa_keys = value ? 1 : 0;    // per-query masked int8 keys
     else if (k == "pqa_bq") idx->pqa_bq = value ? 1 : 0;        // BQ: per-query allow lists share one launch
+    else if (k == "pqa_rq") idx->pqa_rq = value ? 1 : 0;        // rq-8 / rq-1: per-query allow lists share one launch
     else if (k == "bq_fast") idx->bq_fast = value ? 1 : 0;  // replay-free BQ answers when ties cannot matter
     else if (k == "rp_few") idx->rp_few = value;  // replay lists up to this long (device-counted) take the one-launch form
     else if (k == "batch_rows") idx->batch_rows = value ? 1 : 0;  // batcher: dense lists as slot bitmaps
@@ -1054,6 +1055,7 @@ static int search_core(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
         idx->stats.batches++;
         return search_qs(idx, s, nq, k, mode, valid, o_ids, o_d, o_n, o_flags);
     }
+    // (BQ and rq took their own searches above; PQ and SQ never come with per-query bitmaps)
     if (idx->pqa_valid) return set_err(WV_ERR_UNSUPPORTED, "per-query allow lists: block-key route only");
     const int KP = k + idx->margin;
     const bool mfma_ok = KP <= 32 && metric_bilinear(idx->metric) && !idx->force_replay;
@@ -1533,15 +1535,22 @@ static int multi_allow_grouped(wv_index* idx, const float* queries, int64_t nq, 
 }
 
 // the indexes whose multi-allow batch shares one launch: the uncompressed
-// block-key route (search_qs) and, under option pqa_bq, flat + BQ (search_bq:
-// the block minima over the union, each query's R-heap replay over its own
-// bitmap).  rq, PQ and SQ stay grouped by list.
-static bool pqa_bq_route(const wv_index* idx) {
-    return idx->compression == WV_COMPRESSION_BQ && idx->pqa_bq && !idx->rq_bits;
+// block-key route (search_qs) and the quantized flat searches that resolve
+// every query themselves (no flags, no select depths, no per-query keys):
+// under option pqa_bq flat + BQ (search_bq: the block minima over the union,
+// each query's R-heap replay over its own bitmap), under option pqa_rq flat
+// rq-8 / rq-1 on the integer-MFMA route while a launch of nq queries keeps
+// every query's keys (search_rq, rq_pqa_route: union keys, own candidates and
+// replays).  PQ and SQ stay grouped by list.
+static bool pqa_quant_route(const wv_index* idx, int64_t nq, int32_t k) {
+    if (idx->rq_bits) return idx->pqa_rq && rq_pqa_route(idx, nq, k);
+    return idx->compression == WV_COMPRESSION_BQ && idx->pqa_bq;
 }
-static bool pqa_shared(const wv_index* idx, int64_t nq, int64_t d, int32_t k) {
+// qmax: the queries one launch takes (pqa_budget_mb); a longer batch runs as
+// sub-batches of qmax, and it is their size the rq route's one-chunk rule sees
+static bool pqa_shared(const wv_index* idx, int64_t nq, int64_t d, int32_t k, int64_t qmax) {
     if (!idx->pqa || nq <= 1 || idx->dims == 0 || d != idx->dims || k <= 0 || idx->npresent <= 0) return false;
-    if (pqa_bq_route(idx)) return true;
+    if (pqa_quant_route(idx, std::min(nq, qmax), k)) return true;
     return idx->compression == WV_COMPRESSION_NONE && !idx->rq_bits && qs_route(idx, k);
 }
 
@@ -1584,8 +1593,8 @@ static int pqa_run(wv_index* idx, hipStream_t s, const float* queries, int64_t n
     // instead of by the one-wave replay inside the launch, which walks every
     // block key of the union for one query (35 ms at 1M rows, 2 % lists)
     HIPCHK(idx->oF.ensure((size_t)nq * sizeof(int32_t)));
-    // (search_bq resolves every query itself and writes no flags)
-    int32_t* dflags = idx->pqa_alone && !pqa_bq_route(idx) ? idx->oF.as<int32_t>() : nullptr;
+    // (search_bq and search_rq resolve every query themselves and write no flags)
+    int32_t* dflags = idx->pqa_alone && !pqa_quant_route(idx, nq, k) ? idx->oF.as<int32_t>() : nullptr;
     int rc = search_core(idx, s, idx->qraw.as<float>(), nq, d, k, 0, uni, idx->npresent, idx->oIds.as<uint64_t>(),
                          idx->oD.as<float>(), idx->oN.as<int32_t>(), dflags);
     idx->pqa_valid = nullptr;
@@ -1674,8 +1683,8 @@ extern "C" int wv_index_search_by_vector_batch_multi_allow(wv_index* idx, const 
     std::unique_lock<std::mutex> g(idx->mu);
     const int64_t vq = round_up(std::max<int64_t>(idx->hiwater, 1), 256) / 32;  // words per query bitmap
     const int64_t qmax = std::max<int64_t>(1, (idx->pqa_budget_mb << 20) / (vq * (int64_t)sizeof(uint32_t)));
-    const bool fast = pqa_shared(idx, nq, d, k);
-    const bool keyed = fast && !pqa_bq_route(idx);  // the block-key select's depths and split
+    const bool fast = pqa_shared(idx, nq, d, k, qmax);
+    const bool keyed = fast && !pqa_quant_route(idx, std::min(nq, qmax), k);  // the block-key select's depths and split
     if (!fast) {
         g.unlock();
         return multi_allow_grouped(idx, queries, nq, d, k, allow_ids, allow_offsets, allow_modes, out_ids, out_dists,
@@ -1802,8 +1811,8 @@ static int pqa_bitmap_core(wv_index* idx, std::unique_lock<std::mutex>& g, const
     };
     const int64_t vq = round_up(std::max<int64_t>(idx->hiwater, 1), 256) / 32;
     const int64_t qmax = std::max<int64_t>(1, (idx->pqa_budget_mb << 20) / (vq * (int64_t)sizeof(uint32_t) * 2));
-    const bool fast = pqa_shared(idx, nq, d, k) && nq <= qmax;
-    const bool keyed = fast && !pqa_bq_route(idx);  // the block-key select's depths and split
+    const bool fast = pqa_shared(idx, nq, d, k, qmax) && nq <= qmax;
+    const bool keyed = fast && !pqa_quant_route(idx, nq, k);  // the block-key select's depths and split
     std::vector<double> md((size_t)nq, 0.0);
     if (keyed) pqa_depths(idx, nq, k, off.data(), allow_modes, md);
     bool split = false;
