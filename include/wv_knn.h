@@ -284,6 +284,31 @@ int wv_index_hnsw_flat_search(wv_index *idx, const float *queries, int64_t nq, i
                               const uint64_t *allow_ids, int64_t n_allow, int32_t allow_mode, uint64_t *out_ids,
                               float *out_dists, int32_t *out_counts);
 
+/* wv_index_hnsw_flat_search for nq queries, each under its own allow list (the
+ * concurrent filtered callers of shard_read.go:401-424 in one call): query q
+ * uses allow_ids[allow_offsets[q] .. allow_offsets[q+1]) when allow_modes[q] ==
+ * 1 (may be empty -> no results), no list when 0; allow_offsets has nq+1
+ * entries.  Row q equals, bit for bit, a one-query wv_index_hnsw_flat_search
+ * with query q, list q and mode q (ids, distances, count; the ef / rescore
+ * options, the SQ / RQ trim and the rescoring included), and the errors are
+ * that call's, found before any list work.  The listed queries run in list
+ * order: a host planner turns each list -- unsorted, with
+ * duplicates, deleted ids, ids below id_base or at / past the high-water mark
+ * -- into ascending distinct slots (identical lists stored once), k_list_dist
+ * computes the compressor distance of every (query, listed row) and
+ * k_list_heap runs the worker heap over them, so work and distance memory are
+ * the sum of the lists' lengths, never queries x index size
+ * (wv_stats.last_route = WV_ROUTE_LIST_SCAN, last_scan_rows = that sum).  The
+ * batch's mode-0 queries run together through the one-list call's path.
+ * Options: "hnsw_list_rows" (entries per launch group, default 0 = from the
+ * free device memory), "hnsw_list_chunks" (256-entry chunks per workgroup, 0 =
+ * default) and "hnsw_list" (default 0; 1: wv_index_hnsw_flat_search with a
+ * list takes this path too, every query pointing at the one stored list). */
+int wv_index_hnsw_flat_search_multi_allow(wv_index *idx, const float *queries, int64_t nq, int64_t d, int32_t k,
+                                          const uint64_t *allow_ids, const int64_t *allow_offsets,
+                                          const int32_t *allow_modes, uint64_t *out_ids, float *out_dists,
+                                          int32_t *out_counts);
+
 /* Device-resident batch search for sharded / benchmark callers.
  * mode 0: like SearchByVector (kout = k, tie cases resolved by heap replay).
  * mode 1: shard-local candidates: kout = k+1 verified results per query and
@@ -602,6 +627,7 @@ typedef struct wv_stats {
 #define WV_ROUTE_Q8_GEMV 9   /* k_q8_gemv (int8 block keys of <= 32 queries streamed through registers) */
 #define WV_ROUTE_RQ8_INT8 10 /* flat rq-8: k_rq8_keys (exact rq-8 block minima on the integer MFMA) */
 #define WV_ROUTE_L1_TILE 11  /* manhattan: k_l1_rows (register-tiled exact L1 of every row, then the heap replay) */
+#define WV_ROUTE_LIST_SCAN 12 /* hnsw flat search in list order: k_list_dist + k_list_heap over the allow lists' entries */
 int wv_index_stats(wv_index *idx, wv_stats *out);
 
 /* Diagnostic hook (tests): the last MFMA batch's candidates [nq][KP]:

@@ -91,7 +91,7 @@ class WvStats(C.Structure):
 
 # wv_stats.last_route (include/wv_knn.h WV_ROUTE_*)
 ROUTES = {0: "none", 1: "qs_bf16", 2: "qs_w4", 3: "qs_int8", 4: "f32_select", 5: "gemv", 6: "bq_int8", 7: "bq_valu",
-          8: "pq_int8", 9: "q8_gemv", 10: "rq8_int8", 11: "l1_tile"}
+          8: "pq_int8", 9: "q8_gemv", 10: "rq8_int8", 11: "l1_tile", 12: "list_scan"}
 
 
 P = C.c_void_p
@@ -192,6 +192,7 @@ SIGNATURES = {
     "wv_index_sq_info": (C.c_int, [P, pf32]),
     "wv_index_sq_codes": (C.c_int, [P, C.POINTER(C.c_uint8), i64]),
     "wv_index_hnsw_flat_search": (C.c_int, [P, pf32, i64, i64, i32, pu64, i64, i32, pu64, pf32, pi32]),
+    "wv_index_hnsw_flat_search_multi_allow": (C.c_int, [P, pf32, i64, i64, i32, pu64, P, pi32, pu64, pf32, pi32]),
     "wv_index_set_option": (C.c_int, [P, C.c_char_p, i64]),
     "wv_lsm_segment_header": (C.c_int, [C.c_char_p, i32, C.POINTER(C.c_int64)]),
     "wv_lsm_segment_scan": (C.c_int, [C.c_char_p, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),

@@ -1154,13 +1154,53 @@ static int pq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const
     return WV_OK;
 }
 
+// the shared tail of the hnsw flat searches over the worker heaps' ascending
+// extractions ascI / ascD / ascN [nq][R]: k_pq_finish (result heap, SQ / RQ trim),
+// then k_rescore + k_pq_rescore_final when rescoring.  Outputs [nq][k].
+static int hnsw_finish(wv_index* idx, hipStream_t s, int64_t nq, int R, int k, int trim, int rescore, uint64_t* o_ids,
+                       float* o_d, int32_t* o_n) {
+    const int32_t* qlist = idx->ident.as<int32_t>();
+    const float* Qn = idx->qn.as<float>();
+    HIPCHK(idx->cslot.ensure((size_t)nq * R * sizeof(uint32_t)));
+    HIPCHK(idx->cn.ensure((size_t)nq * sizeof(int32_t)));
+    const size_t lds_f = (size_t)R * (sizeof(uint64_t) + sizeof(float)) + 16;
+    if (lds_f > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void*)k_pq_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
+    k_pq_finish<<<(unsigned)nq, 64, lds_f, s>>>(idx->ascI.as<uint64_t>(), idx->ascD.as<float>(), idx->ascN.as<int32_t>(),
+                                                qlist, (int)nq, R, k, rescore, idx->id_base, o_ids, o_d, o_n,
+                                                idx->cslot.as<uint32_t>(), idx->cn.as<int32_t>(), rescore ? trim : 0);
+    HIPCHK(hipGetLastError());
+    if (rescore) {
+        HIPCHK(idx->candE.ensure((size_t)nq * R * sizeof(float)));
+        const int64_t npairs = nq * R;
+        const bool v5 = idx->variant == WV_VARIANT_AVX512;
+#define WV_RS(M, V) k_rescore<M, V><<<(unsigned)((npairs + 63) / 64), 64, 0, s>>>(idx->X, idx->dpad, Qn, idx->dims, idx->cslot.as<uint32_t>(), (int)nq, R, idx->candE.as<float>())
+        switch (idx->metric) {
+        case WV_METRIC_L2_SQUARED: if (v5) WV_RS(L2, AVX512); else WV_RS(L2, AVX256); break;
+        case WV_METRIC_DOT: if (v5) WV_RS(DOT, AVX512); else WV_RS(DOT, AVX256); break;
+        case WV_METRIC_COSINE_DOT: if (v5) WV_RS(COSINE, AVX512); else WV_RS(COSINE, AVX256); break;
+        case WV_METRIC_MANHATTAN: WV_RS(MANHATTAN, AVX256); break;
+        default: WV_RS(HAMMING, AVX256); break;
+        }
+#undef WV_RS
+        HIPCHK(hipGetLastError());
+        const size_t lds_q = (size_t)(k + 1) * (sizeof(uint64_t) + sizeof(float)) + 16;
+        if (lds_q > 64 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)k_pq_rescore_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
+        k_pq_rescore_final<<<(unsigned)nq, 64, lds_q, s>>>(idx->cslot.as<uint32_t>(), idx->candE.as<float>(),
+                                                           idx->cn.as<int32_t>(), qlist, (int)nq, R, k, idx->id_base,
+                                                           o_ids, o_d, o_n);
+        HIPCHK(hipGetLastError());
+    }
+    return WV_OK;
+}
+
 static int search_hnsw(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k, int limit,
                        int trim, int rescore, const uint32_t* valid, uint64_t* o_ids, float* o_d, int32_t* o_n) {
     int comp = 0;
     int rc = hnsw_prep(idx, s, d_qraw, nq, qd, k, &limit, &comp);
     if (rc) return rc;
     const int R = limit;
-    const float* Qn = idx->qn.as<float>();
     const int32_t* qlist = idx->ident.as<int32_t>();
     const int64_t nslots = idx->hiwater;
     const int64_t ld = std::max<int64_t>(round_up(nslots, EBLK), EBLK);
@@ -1312,38 +1352,8 @@ static int search_hnsw(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
         HIPCHK(hipEventRecord(idx->evr[b], idx->aux));
     }
     for (int b = 0; b < 2 && b < gi; b++) HIPCHK(hipStreamWaitEvent(s, idx->evr[b], 0));
-    qlist = idx->ident.as<int32_t>();
-    HIPCHK(idx->cslot.ensure((size_t)nq * R * sizeof(uint32_t)));
-    HIPCHK(idx->cn.ensure((size_t)nq * sizeof(int32_t)));
-    const size_t lds_f = (size_t)R * (sizeof(uint64_t) + sizeof(float)) + 16;
-    if (lds_f > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)k_pq_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-    k_pq_finish<<<(unsigned)nq, 64, lds_f, s>>>(idx->ascI.as<uint64_t>(), idx->ascD.as<float>(), idx->ascN.as<int32_t>(),
-                                                qlist, (int)nq, R, k, rescore, idx->id_base, o_ids, o_d, o_n,
-                                                idx->cslot.as<uint32_t>(), idx->cn.as<int32_t>(), rescore ? trim : 0);
-    HIPCHK(hipGetLastError());
-    if (rescore) {
-        HIPCHK(idx->candE.ensure((size_t)nq * R * sizeof(float)));
-        const int64_t npairs = nq * R;
-        const bool v5 = idx->variant == WV_VARIANT_AVX512;
-#define WV_RS(M, V) k_rescore<M, V><<<(unsigned)((npairs + 63) / 64), 64, 0, s>>>(idx->X, idx->dpad, Qn, idx->dims, idx->cslot.as<uint32_t>(), (int)nq, R, idx->candE.as<float>())
-        switch (idx->metric) {
-        case WV_METRIC_L2_SQUARED: if (v5) WV_RS(L2, AVX512); else WV_RS(L2, AVX256); break;
-        case WV_METRIC_DOT: if (v5) WV_RS(DOT, AVX512); else WV_RS(DOT, AVX256); break;
-        case WV_METRIC_COSINE_DOT: if (v5) WV_RS(COSINE, AVX512); else WV_RS(COSINE, AVX256); break;
-        case WV_METRIC_MANHATTAN: WV_RS(MANHATTAN, AVX256); break;
-        default: WV_RS(HAMMING, AVX256); break;
-        }
-#undef WV_RS
-        HIPCHK(hipGetLastError());
-        const size_t lds_q = (size_t)(k + 1) * (sizeof(uint64_t) + sizeof(float)) + 16;
-        if (lds_q > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)k_pq_rescore_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-        k_pq_rescore_final<<<(unsigned)nq, 64, lds_q, s>>>(idx->cslot.as<uint32_t>(), idx->candE.as<float>(),
-                                                           idx->cn.as<int32_t>(), qlist, (int)nq, R, k, idx->id_base,
-                                                           o_ids, o_d, o_n);
-        HIPCHK(hipGetLastError());
-    }
+    rc = hnsw_finish(idx, s, nq, R, k, trim, rescore, o_ids, o_d, o_n);
+    if (rc) return rc;
     if (idx->timing) {
         HIPCHK(hipStreamSynchronize(s));
         float ms = 0.f;
@@ -1376,15 +1386,184 @@ static int hnsw_search_ef(const wv_index* idx, int k) {
 }
 
 // hnsw.SearchByVector's flat branch for a compressed index: limit / trim / rescore
-int search_hnsw_flat(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k,
-                            const uint32_t* valid, uint64_t* o_ids, float* o_d, int32_t* o_n) {
+static void hnsw_flat_params(const wv_index* idx, int k, int* limit, int* trim, int* rescore_out) {
     const bool sqrq = idx->compression == WV_COMPRESSION_SQ || idx->rq_bits != 0;
     // shouldRescore (search.go:182-189); a PQ index created with pq_rescore = 0 counts as doNotRescore
     bool rescore = idx->hnsw_rescore != 0 && !(sqrq && idx->rescore_limit == 0);
     if (idx->compression == WV_COMPRESSION_PQ && !idx->pq_rescore) rescore = false;
-    const int limit = rescore ? hnsw_search_ef(idx, k) : k;  // flat_search.go:31-33
-    const int trim = (sqrq && idx->rescore_limit >= k) ? idx->rescore_limit : 0;
-    return search_hnsw(idx, s, d_qraw, nq, qd, k, limit, trim, rescore ? 1 : 0, valid, o_ids, o_d, o_n);
+    *limit = rescore ? hnsw_search_ef(idx, k) : k;  // flat_search.go:31-33
+    *trim = (sqrq && idx->rescore_limit >= k) ? idx->rescore_limit : 0;
+    *rescore_out = rescore ? 1 : 0;
+}
+
+int search_hnsw_flat(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k,
+                            const uint32_t* valid, uint64_t* o_ids, float* o_d, int32_t* o_n) {
+    int limit = 0, trim = 0, rescore = 0;
+    hnsw_flat_params(idx, k, &limit, &trim, &rescore);
+    return search_hnsw(idx, s, d_qraw, nq, qd, k, limit, trim, rescore, valid, o_ids, o_d, o_n);
+}
+
+// hnsw.SearchByVector's flat branch in list order: every
+// query q of the batch has its own allow list ids[lo[q] .. hi[q]).  The work
+// and the distance memory are the lists' sizes, not the index's: hnsw_prep for
+// the batch, the host plan (list_plan.h: ascending distinct in-range slots,
+// shared storage, work table, launch groups), per group k_list_dist on the
+// main stream and k_list_heap on idx->aux beside the next group's distance
+// kernel (two buffers, the events of search_hnsw), then the shared finish and
+// rescore stages.  limit / trim / rescore as search_hnsw_flat; outputs [nq][k].
+int search_hnsw_lists(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k,
+                      const uint64_t* ids, const int64_t* lo, const int64_t* hi, uint64_t* o_ids, float* o_d,
+                      int32_t* o_n) {
+    int limit = 0, trim = 0, rescore = 0, comp = 0;
+    hnsw_flat_params(idx, k, &limit, &trim, &rescore);
+    int rc = hnsw_prep(idx, s, d_qraw, nq, qd, k, &limit, &comp);
+    if (rc) return rc;
+    const int R = limit;
+    HIPCHK(idx->ascI.ensure((size_t)nq * R * sizeof(uint64_t)));
+    HIPCHK(idx->ascD.ensure((size_t)nq * R * sizeof(float)));
+    HIPCHK(idx->ascN.ensure((size_t)nq * sizeof(int32_t)));
+    // entries per launch group: two distance buffers within the free HBM
+    // (as search_hnsw sizes its query groups), or option hnsw_list_rows
+    int64_t budget = idx->hnsw_list_rows;
+    if (budget <= 0) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        const int64_t have = (int64_t)(Eb0_bytes(idx) + free_b / 4);
+        budget = std::max<int64_t>(std::min<int64_t>(16ll << 30, have), 1ll << 30) / (int64_t)sizeof(float);
+    }
+    const bool pq = comp == WV_COMPRESSION_PQ;
+    int cpw = idx->hnsw_list_chunks;
+    if (pq) cpw = cpw == 4 || cpw == 8 ? cpw : LIST_PQ_CPW;
+    else if (cpw <= 0) cpw = LIST_CPW;
+    const ListPlan plan = list_plan(ids, lo, hi, nq, idx->id_base, idx->hiwater, budget, cpw);
+    idx->stats.last_route = WV_ROUTE_LIST_SCAN;
+    idx->stats.last_scan_rows = (uint64_t)plan.scanned;
+    idx->stats.last_group_queries = plan.groups.empty() ? 0 : (uint64_t)(plan.groups[0].lq1 - plan.groups[0].lq0);
+    HIPCHK(idx->lsPool.ensure(plan.pool.size() * sizeof(uint32_t)));
+    HIPCHK(idx->lsQ.ensure(plan.queries.size() * sizeof(ListQuery)));
+    HIPCHK(idx->lsPiece.ensure(plan.pieces.size() * sizeof(ListPiece)));
+    if (!plan.pool.empty())
+        HIPCHK(hipMemcpyAsync(idx->lsPool.p, plan.pool.data(), plan.pool.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (!plan.queries.empty())
+        HIPCHK(hipMemcpyAsync(idx->lsQ.p, plan.queries.data(), plan.queries.size() * sizeof(ListQuery), hipMemcpyHostToDevice, s));
+    if (!plan.pieces.empty())
+        HIPCHK(hipMemcpyAsync(idx->lsPiece.p, plan.pieces.data(), plan.pieces.size() * sizeof(ListPiece), hipMemcpyHostToDevice, s));
+    rc = ensure_aux(idx);
+    if (rc) return rc;
+    DBuf* Eb[2] = {&idx->rE, &idx->rE2};
+    DBuf* Bb[2] = {&idx->rB, &idx->rB2};
+    DBuf* Ab[2] = {&idx->lsAb, &idx->lsAb2};
+    const int64_t me = std::max<int64_t>(plan.max_entries, LIST_CHUNK);
+    for (int b = 0; b < 2 && b < (int)plan.groups.size(); b++) {
+        HIPCHK(Eb[b]->ensure((size_t)me * sizeof(float)));
+        HIPCHK(Bb[b]->ensure((size_t)(me / LIST_CHUNK) * sizeof(float)));
+        HIPCHK(Ab[b]->ensure((size_t)(me / 64) * sizeof(uint64_t)));
+    }
+    ListDistArgs a{};
+    a.pool = idx->lsPool.as<uint32_t>();
+    a.lq = idx->lsQ.as<ListQuery>();
+    a.present = idx->present;
+    a.cap = idx->cap;
+    a.nq = nq;
+    a.metric = idx->metric == WV_METRIC_L2_SQUARED ? L2 : idx->metric == WV_METRIC_DOT ? DOT : COSINE;
+    size_t lds = 0;
+    int kind = LC_BQ;
+    if (pq) {
+        kind = idx->pq_ks == 256 ? LC_PQ256 : LC_PQ;
+        a.codes = idx->pq_codes;
+        a.qcodes = idx->lut.p;
+        a.D = idx->pq_m;
+        a.K = idx->pq_ks;
+        a.g16 = pq_g16(idx->pq_m);
+        lds = (size_t)PQ_CH * idx->pq_ks * sizeof(float);
+    } else if (comp == WV_COMPRESSION_RQ8) {  // rq-8 and rq-1
+        kind = idx->rq_bits == 8 ? LC_RQ8 : LC_RQ1;
+        a.codes = idx->rq_codes;
+        a.meta = idx->rq_meta;
+        a.qcodes = idx->rqq.p;
+        a.qmeta = idx->rqm.p;
+        a.D = idx->rq_D;
+        a.f0 = idx->metric == WV_METRIC_L2_SQUARED ? 1.f : 0.f;
+        a.f1 = idx->metric == WV_METRIC_COSINE_DOT ? 1.f : 0.f;
+        lds = (size_t)rq_query_lds_u4(idx->rq_bits, idx->rq_D) * sizeof(uint4);
+    } else if (comp == WV_COMPRESSION_SQ) {
+        kind = LC_SQ;
+        a.codes = idx->sq_codes;
+        a.meta = idx->sq_meta;
+        a.qcodes = idx->sqq.p;
+        a.qmeta = idx->sqm.p;
+        a.D = idx->sq_Dq;
+        a.f0 = idx->sq_a2;
+        a.f1 = idx->sq_ab;
+        a.f2 = idx->sq_ib2;
+        lds = (size_t)idx->sq_Dq;
+    } else {
+        a.codes = idx->codes;
+        a.qcodes = idx->qcodes.p;
+        a.D = idx->words;
+        lds = (size_t)idx->words * sizeof(uint64_t);
+    }
+    const size_t lds_h = replay_scan_lds(R);
+    const bool pk = R <= PACKED_REPLAY_MAX_K;
+    if (lds_h > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute(pk ? (const void*)k_list_heap<true> : (const void*)k_list_heap<false>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h));
+    int64_t gi = 0;
+    for (const ListGroup& g : plan.groups) {
+        const int b = (int)(gi & 1);
+        if (gi >= 2) HIPCHK(hipStreamWaitEvent(s, idx->evr[b], 0));
+        a.Ec = Eb[b]->as<float>();
+        a.Bc = Bb[b]->as<float>();
+        a.Ab = Ab[b]->as<uint64_t>();
+        a.pieces = idx->lsPiece.as<ListPiece>() + g.piece0;
+        const unsigned np = (unsigned)(g.piece1 - g.piece0);
+        const bool time_it = idx->timing && gi == 0;
+        if (time_it) HIPCHK(hipEventRecord(idx->ev0, s));
+        if (np > 0) {
+            switch (kind) {
+            case LC_BQ: k_list_dist<LC_BQ><<<np, 256, lds, s>>>(a); break;
+            case LC_SQ: k_list_dist<LC_SQ><<<np, 256, lds, s>>>(a); break;
+            case LC_RQ8: k_list_dist<LC_RQ8><<<np, 256, lds, s>>>(a); break;
+            case LC_RQ1: k_list_dist<LC_RQ1><<<np, 256, lds, s>>>(a); break;
+            case LC_PQ:
+                if (cpw == 4) k_list_dist<LC_PQ, 4><<<np, 256, lds, s>>>(a);
+                else if (cpw == 8) k_list_dist<LC_PQ, 8><<<np, 256, lds, s>>>(a);
+                else k_list_dist<LC_PQ, LIST_PQ_CPW><<<np, 256, lds, s>>>(a);
+                break;
+            default:
+                if (cpw == 4) k_list_dist<LC_PQ256, 4><<<np, 256, lds, s>>>(a);
+                else if (cpw == 8) k_list_dist<LC_PQ256, 8><<<np, 256, lds, s>>>(a);
+                else k_list_dist<LC_PQ256, LIST_PQ_CPW><<<np, 256, lds, s>>>(a);
+                break;
+            }
+            HIPCHK(hipGetLastError());
+        }
+        if (time_it) HIPCHK(hipEventRecord(idx->ev1, s));
+        HIPCHK(hipEventRecord(idx->evd[b], s));
+        HIPCHK(hipStreamWaitEvent(idx->aux, idx->evd[b], 0));
+        const unsigned nl = (unsigned)(g.lq1 - g.lq0);
+        if (pk)
+            k_list_heap<true><<<nl, 64, lds_h, idx->aux>>>(a.Ec, a.Bc, a.Ab, a.pool, a.lq + g.lq0, (int)nl, R, idx->id_base,
+                                                          idx->ascI.as<uint64_t>(), idx->ascD.as<float>(),
+                                                          idx->ascN.as<int32_t>());
+        else
+            k_list_heap<false><<<nl, 64, lds_h, idx->aux>>>(a.Ec, a.Bc, a.Ab, a.pool, a.lq + g.lq0, (int)nl, R,
+                                                           idx->id_base, idx->ascI.as<uint64_t>(),
+                                                           idx->ascD.as<float>(), idx->ascN.as<int32_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(idx->evr[b], idx->aux));
+        gi++;
+    }
+    for (int b = 0; b < 2 && b < gi; b++) HIPCHK(hipStreamWaitEvent(s, idx->evr[b], 0));
+    rc = hnsw_finish(idx, s, nq, R, k, trim, rescore, o_ids, o_d, o_n);
+    if (rc) return rc;
+    if (idx->timing) {
+        HIPCHK(hipStreamSynchronize(s));
+        float ms = 0.f;
+        if (gi > 0) hipEventElapsedTime(&ms, idx->ev0, idx->ev1);
+        idx->stats.last_select_ms = ms;
+    }
+    return WV_OK;
 }
 
 // ---- sharded hnsw flat search over compressed vectors (weaviate_amd/sharded.py

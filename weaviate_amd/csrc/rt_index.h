@@ -29,6 +29,7 @@
 
 #include "../../include/wv_knn.h"
 #include "key_plan.h"
+#include "list_plan.h"
 #include "kernels.hip"
 #include "l1_kernels.hip"
 #include "bq_kernels.hip"
@@ -40,6 +41,7 @@
 #include "q8_kernels.hip"
 #include "rq8_mfma.hip"
 #include "sq_kernels.hip"
+#include "list_kernels.hip"
 
 using namespace wv;
 
@@ -204,6 +206,11 @@ struct wv_index {
     DBuf sqq, sqm;                // query codes / meta
     // hnsw.flatSearch parameters (wv_index_hnsw_flat_search)
     int hnsw_ef = -1, ef_min = 100, ef_max = 500, ef_factor = 8, hnsw_rescore = 1;
+    // the list-order hnsw flat search (search_hnsw_lists)
+    int hnsw_list = 0;            // option hnsw_list: wv_index_hnsw_flat_search's one list takes the list path too
+    int64_t hnsw_list_rows = 0;   // option hnsw_list_rows: entries per launch group (0: from the free HBM)
+    int hnsw_list_chunks = 0;     // option hnsw_list_chunks: 256-entry chunks per workgroup (0: LIST_CPW / LIST_PQ_CPW)
+    DBuf lsPool, lsQ, lsPiece, lsAb, lsAb2;  // the plan on the device, the absent bits of the two distance buffers
     std::vector<uint8_t> h_present;
     uint64_t count = 0;    // flat.count: incremented per Add (flat/index.go:380-385)
     int64_t npresent = 0;
@@ -411,6 +418,9 @@ int search_pq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
               uint64_t* o_ids, float* o_d, int32_t* o_n);
 int search_hnsw_flat(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k,
                      const uint32_t* valid, uint64_t* o_ids, float* o_d, int32_t* o_n);
+int search_hnsw_lists(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k,
+                      const uint64_t* ids, const int64_t* lo, const int64_t* hi, uint64_t* o_ids, float* o_d,
+                      int32_t* o_n);
 int pq_fit_rows(wv_index* idx, const float* dT, int64_t n, uint64_t seed);
 int64_t bq_max_batch(const wv_index* idx);
 bool rq_pqa_route(const wv_index* idx, int64_t nq, int k);

@@ -791,6 +791,9 @@ extern "C" int wv_index_set_option(wv_index* idx, const char* key, int64_t value
     else if (k == "pqa_keys") idx->pqa_keys = value ? 1 : 0;    // per-query masked int8 keys
     else if (k == "pqa_bq") idx->pqa_bq = value ? 1 : 0;        // BQ: per-query allow lists share one launch
     else if (k == "pqa_rq") idx->pqa_rq = value ? 1 : 0;        // rq-8 / rq-1: per-query allow lists share one launch
+    else if (k == "hnsw_list") idx->hnsw_list = value ? 1 : 0;  // hnsw flat search: the one-list call takes the list path
+    else if (k == "hnsw_list_rows") idx->hnsw_list_rows = std::max<int64_t>(value, 0);  // list path: entries per launch group (0 = auto)
+    else if (k == "hnsw_list_chunks") idx->hnsw_list_chunks = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 64);  // chunks per workgroup (0 = default)
     else if (k == "bq_fast") idx->bq_fast = value ? 1 : 0;  // replay-free BQ answers when ties cannot matter
     else if (k == "rp_few") idx->rp_few = value;  // replay lists up to this long (device-counted) take the one-launch form
     else if (k == "batch_rows") idx->batch_rows = value ? 1 : 0;  // batcher: dense lists as slot bitmaps
@@ -1924,18 +1927,47 @@ static int batch_search_slot_bitmaps(wv_index* idx, const float* queries, int64_
     return pqa_bitmap_core(idx, g, queries, nq, d, k, modes.data(), off, fill, lists, out_ids, out_dists, out_counts);
 }
 
-extern "C" int wv_index_hnsw_flat_search(wv_index* idx, const float* queries, int64_t nq, int64_t d, int32_t k,
-                                         const uint64_t* allow_ids, int64_t n_allow, int32_t allow_mode,
-                                         uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
-    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
+// every query of the batch under its own list ids[lo[q] .. hi[q]), in list
+// order (search_hnsw_lists); mu held.  An index without rows answers as the
+// one-query call does.
+static int hnsw_lists_locked(wv_index* idx, const float* queries, int64_t nq, int64_t d, int32_t k, const uint64_t* ids,
+                             const int64_t* lo, const int64_t* hi, uint64_t* out_ids, float* out_dists,
+                             int32_t* out_counts) {
+    hipStream_t s = idx->stream;
+    if (idx->dims == 0 || idx->npresent == 0 || nq <= 0) {
+        for (int64_t q = 0; q < nq; q++) out_counts[q] = 0;
+        return WV_OK;
+    }
+    const int kk = std::max(k, 1);
+    HIPCHK(idx->qraw.ensure((size_t)nq * d * sizeof(float)));
+    HIPCHK(idx->oIds.ensure((size_t)nq * kk * sizeof(uint64_t)));
+    HIPCHK(idx->oD.ensure((size_t)nq * kk * sizeof(float)));
+    HIPCHK(idx->oN.ensure((size_t)nq * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(idx->qraw.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, s));
+    int rc = search_hnsw_lists(idx, s, idx->qraw.as<float>(), nq, d, k, ids, lo, hi, idx->oIds.as<uint64_t>(),
+                               idx->oD.as<float>(), idx->oN.as<int32_t>());
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out_ids, idx->oIds.p, (size_t)nq * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_dists, idx->oD.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_counts, idx->oN.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return WV_OK;
+}
+
+// wv_index_hnsw_flat_search with mu held
+static int hnsw_flat_locked(wv_index* idx, const float* queries, int64_t nq, int64_t d, int32_t k,
+                            const uint64_t* allow_ids, int64_t n_allow, int32_t allow_mode, uint64_t* out_ids,
+                            float* out_dists, int32_t* out_counts) {
     if (idx->compression == WV_COMPRESSION_NONE)
         return set_err(WV_ERR_UNSUPPORTED, "hnsw flat search: index is not compressed (use SearchByVector)");
     hipStream_t s = idx->stream;
     if (allow_mode == 1 && n_allow == 0) {
         for (int64_t q = 0; q < nq; q++) out_counts[q] = 0;
         return WV_OK;
+    }
+    if (allow_mode == 1 && idx->hnsw_list) {  // option hnsw_list: every query points at the one list
+        const std::vector<int64_t> lo((size_t)std::max<int64_t>(nq, 1), 0), hi((size_t)std::max<int64_t>(nq, 1), n_allow);
+        return hnsw_lists_locked(idx, queries, nq, d, k, allow_ids, lo.data(), hi.data(), out_ids, out_dists, out_counts);
     }
     const uint32_t* valid = nullptr;
     int64_t n_valid = 0;
@@ -1958,6 +1990,69 @@ extern "C" int wv_index_hnsw_flat_search(wv_index* idx, const float* queries, in
     HIPCHK(hipMemcpyAsync(out_dists, idx->oD.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(out_counts, idx->oN.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return WV_OK;
+}
+
+extern "C" int wv_index_hnsw_flat_search(wv_index* idx, const float* queries, int64_t nq, int64_t d, int32_t k,
+                                         const uint64_t* allow_ids, int64_t n_allow, int32_t allow_mode,
+                                         uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
+    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHK(hipSetDevice(idx->device));
+    return hnsw_flat_locked(idx, queries, nq, d, k, allow_ids, n_allow, allow_mode, out_ids, out_dists, out_counts);
+}
+
+// The concurrent filtered callers of hnsw.SearchByVector's flat branch in one
+// call: the listed queries (mode 1) go through search_hnsw_lists, the batch's
+// mode-0 queries together through the existing search over `present`; rows
+// are scattered into the outputs once both succeeded.
+extern "C" int wv_index_hnsw_flat_search_multi_allow(wv_index* idx, const float* queries, int64_t nq, int64_t d,
+                                                     int32_t k, const uint64_t* allow_ids,
+                                                     const int64_t* allow_offsets, const int32_t* allow_modes,
+                                                     uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
+    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHK(hipSetDevice(idx->device));
+    if (idx->compression == WV_COMPRESSION_NONE)
+        return set_err(WV_ERR_UNSUPPORTED, "hnsw flat search: index is not compressed (use SearchByVector)");
+    if (nq <= 0) return WV_OK;
+    std::vector<int64_t> rows[2], lo, hi;  // [0]: mode-0 rows, [1]: listed rows
+    for (int64_t q = 0; q < nq; q++) {
+        const int m = allow_modes[q] ? 1 : 0;
+        rows[m].push_back(q);
+        if (m) { lo.push_back(allow_offsets[q]); hi.push_back(allow_offsets[q + 1]); }
+    }
+    if (rows[0].empty())
+        return hnsw_lists_locked(idx, queries, nq, d, k, allow_ids, lo.data(), hi.data(), out_ids, out_dists, out_counts);
+    const int kk = std::max(k, 1);
+    std::vector<float> qb[2];
+    std::vector<uint64_t> oi[2];
+    std::vector<float> od[2];
+    std::vector<int32_t> on[2];
+    for (int m = 0; m < 2; m++) {
+        const int64_t n = (int64_t)rows[m].size();
+        if (n == 0) continue;
+        qb[m].resize((size_t)(n * std::max<int64_t>(d, 1)));
+        for (int64_t i = 0; i < n; i++)
+            if (d > 0) memcpy(&qb[m][(size_t)(i * d)], queries + rows[m][(size_t)i] * d, (size_t)d * sizeof(float));
+        oi[m].resize((size_t)(n * kk));
+        od[m].resize((size_t)(n * kk));
+        on[m].resize((size_t)n);
+        const int rc = m ? hnsw_lists_locked(idx, qb[m].data(), n, d, k, allow_ids, lo.data(), hi.data(), oi[m].data(),
+                                             od[m].data(), on[m].data())
+                         : hnsw_flat_locked(idx, qb[m].data(), n, d, k, nullptr, 0, 0, oi[m].data(), od[m].data(),
+                                            on[m].data());
+        if (rc) return rc;
+    }
+    for (int m = 0; m < 2; m++)
+        for (size_t i = 0; i < rows[m].size(); i++) {
+            const int64_t q = rows[m][i];
+            out_counts[q] = on[m][i];
+            for (int j = 0; j < on[m][i] && j < k; j++) {
+                out_ids[q * k + j] = oi[m][i * (size_t)k + (size_t)j];
+                out_dists[q * k + j] = od[m][i * (size_t)k + (size_t)j];
+            }
+        }
     return WV_OK;
 }
 
