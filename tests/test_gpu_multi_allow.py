@@ -144,14 +144,20 @@ def test_batcher_coalesces_distinct_allow_lists(wv, oracle):
     idx.close()
 
 
-@pytest.mark.parametrize("opts,k,nq", [({"pqa_budget_mb": 1}, 10, 200),     # bitmap budget: sub-batches (offsets q0 * k)
+# a 1 MiB bitmap budget at n = 30000: a query's bitmap is round_up(30000, 256) / 32 = 944 words = 3776 bytes, so a
+# launch built from id lists takes 1048576 / 3776 = 277 queries and one built from the callers' bitmaps 138
+SEAM_ROWS = sorted(set(range(9)) | set(range(275, 280)) | {299})  # every list kind, the seam at 277, the end
+
+
+@pytest.mark.parametrize("opts,k,nq", [({"pqa_budget_mb": 1}, 10, 300),     # bitmap budget: sub-batches of 277 + 23 (offsets q0 * k)
                                        ({"sel_lower": 1}, 10, 64),           # the select's lowered thresholds
                                        ({}, 1000, 24),                       # k > 959: 1984-block lists, R = 32
                                        ({"pqa_split_max": 0, "pqa_alone": 0}, 300, 40)])
 def test_multi_allow_option_paths_equal_one_query_calls(wv, oracle, opts, k, nq):
     """The multi-allow paths ADVICE r5 listed as untested: the per-query bitmap
-    budget's sub-batch recursion, sel_lower = 1, large k with per-query
-    bitmaps; each against the one-query calls."""
+    budget's sub-batches (a sample of the 300 rows: every list kind, the rows
+    at the cut and the last), sel_lower = 1, large k with per-query bitmaps;
+    each against the one-query calls."""
     n, d = 30000, 128
     data = oracle.gen_matrix(1, 73, 0, n, d)  # integer data: ties, replays
     queries = oracle.gen_matrix(1, 74, 0, nq, d)
@@ -161,7 +167,7 @@ def test_multi_allow_option_paths_equal_one_query_calls(wv, oracle, opts, k, nq)
         idx.set_option(kk, vv)
     allows = _allow_lists(wv, n, nq, min(k, 64), seed=7 + k)
     ids, dists, counts = idx.search_by_vector_batch_multi_allow(queries, k, allows)
-    for i in range(nq):
+    for i in (SEAM_ROWS if nq == 300 else range(nq)):
         ei, ed, ec = idx.search_by_vector_batch(queries[i:i + 1], k, allow=allows[i])
         assert counts[i] == ec[0], f"q{i}"
         np.testing.assert_array_equal(ids[i, :counts[i]], ei[0, :ec[0]], err_msg=f"q{i}")
@@ -173,14 +179,14 @@ def test_multi_allow_option_paths_equal_one_query_calls(wv, oracle, opts, k, nq)
 @pytest.mark.parametrize("id_base,opts,k,nq", [(0, {}, 10, 54),
                                                (1000013, {}, 10, 45),                       # unaligned shard base
                                                (64, {"pqa_split_max": 0, "pqa_alone": 0}, 32, 40),
-                                               (0, {"pqa_budget_mb": 1}, 10, 120),           # sub-batches: via lists
+                                               (0, {"pqa_budget_mb": 1}, 10, 300),           # n = 30000, 300 > 138: via lists, cut at 277
                                                (0, {}, 300, 30)])
 def test_multi_allow_bitmap_form_equals_id_lists(wv, oracle, id_base, opts, k, nq):
     """wv_index_search_by_vector_batch_multi_allow_bitmap: the same lists as
     dense doc-id bitmaps give the id-list call's rows (and the oracle's), on an
     index whose doc ids start at id_base (a shard): the bitmap words are read
     from id_base on with the bit shift id_base % 32."""
-    n, d = 20000, 128
+    n, d = (30000 if nq == 300 else 20000), 128
     data = oracle.gen_matrix(1, 81, 0, n, d)  # integer data: ties
     queries = oracle.gen_matrix(1, 82, 0, nq, d)
     idx = wv.FlatIndex(distance="l2-squared", variant="avx256", id_base=id_base)
@@ -200,12 +206,79 @@ def test_multi_allow_bitmap_form_equals_id_lists(wv, oracle, id_base, opts, k, n
     orc = oracle.OracleFlat(oracle.METRIC["l2-squared"], 1, d, n)
     orc.add_batch(np.arange(n, dtype=np.uint64), data)
     orc.delete(list(range(3, n, 101)))
-    for i in range(min(nq, 12)):
+    for i in (SEAM_ROWS if nq == 300 else range(min(nq, 12))):
+        if nq == 300:  # the one-query call too, at the seam
+            ei, ed, ec = idx.search_by_vector_batch(queries[i:i + 1], k, allow=allows[i])
+            assert bc[i] == ec[0], f"q{i}"
+            np.testing.assert_array_equal(bi[i, :bc[i]], ei[0, :ec[0]], err_msg=f"q{i}")
+            np.testing.assert_array_equal(bd[i, :bc[i]].view(np.uint32), ed[0, :ec[0]].view(np.uint32), err_msg=f"q{i}")
         al = None if base[i] is None else [int(x) for x in base[i].ids]
         rc, oi, od = orc.search(queries[i], k, al)
         np.testing.assert_array_equal(bi[i, :bc[i]], oi.astype(np.uint64) + np.uint64(id_base), err_msg=f"q{i}")
         np.testing.assert_array_equal(bd[i, :bc[i]].view(np.uint32), od.view(np.uint32), err_msg=f"q{i}")
     idx.close()
+
+
+@pytest.fixture(scope="module")
+def seam_batch(wv, oracle):
+    """300 queries on a fresh index of 30000 rows under a 1 MiB bitmap budget
+    (launches of at most 277 queries), first with every list kept in the shared
+    launches (no split, no query searched alone afterwards): that call's rows
+    are what every other form of the batch must give."""
+    n, d, k, nq = 30000, 128, 10, 300
+    data = oracle.gen_matrix(1, 73, 0, n, d)  # integer data: ties, replays
+    queries = oracle.gen_matrix(1, 74, 0, nq, d)
+    idx = wv.FlatIndex(distance="l2-squared", variant="avx256")
+    idx.add_batch(np.arange(n, dtype=np.uint64), data)
+    allows = _allow_lists(wv, n, nq, k, seed=17)
+    idx.set_option("pqa_budget_mb", 1)
+    idx.set_option("pqa_split_max", 0)
+    idx.set_option("pqa_alone", 0)
+    b0 = idx.stats()["batches"]
+    first = idx.search_by_vector_batch_multi_allow(queries, k, allows)
+    launches = idx.stats()["batches"] - b0
+    idx.set_option("pqa_split_max", 64)  # the defaults
+    idx.set_option("pqa_alone", 1)
+    yield idx, queries, k, allows, first, launches
+    idx.close()
+
+
+@pytest.mark.parametrize("form", ["ids", "bitmap", "batcher"])
+def test_multi_allow_budget_cut_split_and_flags_in_one_batch(seam_batch, form):
+    """One batch that is cut by the bitmap budget (277 + 23 queries), loses its
+    too-sparse lists to the split and has flagged queries searched alone: as id
+    lists, as dense bitmaps (300 > 138: through lists) and as concurrent
+    one-query calls through the batcher's slot-bitmap rows, all 300 rows equal
+    the rows of the launches that kept every list."""
+    idx, queries, k, allows, (ids, dists, counts), launches = seam_batch
+    nq = len(queries)
+    if form == "ids":
+        assert launches == 2, "300 queries at 277 per launch: two launches"
+        gi, gd, gc = idx.search_by_vector_batch_multi_allow(queries, k, allows)
+    elif form == "bitmap":
+        gi, gd, gc = idx.search_by_vector_batch_multi_allow(queries, k, allows, bitmap=True)
+    else:
+        idx.set_option("batch_rows", 1)  # (the default)
+        idx.set_option("batch_window_us", 20000)
+        b0 = idx.batcher_stats()
+        try:
+            with ThreadPoolExecutor(nq) as ex:
+                res = list(ex.map(lambda i: idx.search_by_vector(queries[i], k, allow=allows[i]), range(nq)))
+        finally:
+            idx.set_option("batch_window_us", 1000)  # the default: the other cases see the index as the fixture left it
+        b1 = idx.batcher_stats()
+        assert b1["calls"] - b0["calls"] == nq and b1["launches"] - b0["launches"] < nq and b1["max_batch"] > 1, (b0, b1)
+        gc = np.array([len(r[0]) for r in res], dtype=np.int32)
+        gi = np.zeros_like(ids)
+        gd = np.zeros_like(dists)
+        for i, (ri, rd) in enumerate(res):
+            gi[i, :len(ri)] = ri
+            gd[i, :len(rd)] = rd
+    np.testing.assert_array_equal(gc, counts)
+    for i in range(nq):
+        np.testing.assert_array_equal(gi[i, :counts[i]], ids[i, :counts[i]], err_msg=f"q{i}")
+        np.testing.assert_array_equal(gd[i, :counts[i]].view(np.uint32), dists[i, :counts[i]].view(np.uint32),
+                                      err_msg=f"q{i}")
 
 
 @pytest.mark.parametrize("metric,kind,d,k,nq", [("cosine", 0, 768, 10, 300),

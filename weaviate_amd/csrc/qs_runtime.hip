@@ -135,7 +135,8 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
     const int NC8 = idx->dpb8 / 64;
     const int RB8 = idx->dpb8 <= 768 ? 2 : 1;
     const int RB = q8 ? RB8 : qs_rb(NK);
-    const bool pqa = idx->pqa_valid != nullptr;
+    const PqaBatch* pb = idx->pqa_cur;  // a multi-allow batch's shared launch (pqa_run)
+    const bool pqa = pb != nullptr;
     // per-query keys (option pqa_keys, int8 paired dot / cosine keys): the key
     // pass masks each query's rows with its own bitmap (k_q8_blockkey<..,
     // MASK>), so every key bounds the query's own rows and the plain select,
@@ -149,7 +150,7 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
         if (idx->q8_R > 0) R = std::max(R, idx->q8_R);
         else R = std::max(R, 8);
     }
-    if (pqs) R = std::max(R, idx->pqa_R);  // per-query lists on the union's keys: deeper thresholds (k_blk_select mq)
+    if (pqs) R = std::max(R, pb->R);  // per-query lists on the union's keys: deeper thresholds (k_blk_select mq)
     const int L = 64 * (R - 1);
     const int64_t nslots = std::max<int64_t>(1, (idx->hiwater + 32 * RB - 1) / (32 * RB));
     const int64_t nb = nslots * RB;  // 32-row blocks scanned = key row length
@@ -162,7 +163,7 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
     HIPCHK(idx->qsInfo.ensure((size_t)qc * sizeof(float4)));
     HIPCHK(idx->qsKey.ensure((size_t)qc * ldk * sizeof(float)));
     // 448: the overflow pass; 960: per-query lists' second pass
-    HIPCHK(idx->qsCand.ensure((size_t)qc * std::max(L, idx->pqa_valid ? 960 : 448) * sizeof(uint32_t)));
+    HIPCHK(idx->qsCand.ensure((size_t)qc * std::max(L, pqa ? 960 : 448) * sizeof(uint32_t)));
     HIPCHK(idx->qsNc.ensure((size_t)qc * sizeof(int32_t)));
     HIPCHK(idx->qsEps.ensure((size_t)qc * sizeof(float)));
     if (q8) {
@@ -212,8 +213,11 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
         if (c0 == 0) { idx->qs_last_nq = cn == nq ? cn : 0; idx->qs_last_nb = nb; idx->qs_last_ldk = ldk; }
         const float* Qn = Qn_all + c0 * idx->dpad;
         // the exact pass's and the replays' row bitmap(s)
-        const uint32_t* exv = pqa ? idx->pqa_valid + c0 * idx->pqa_vq : valid;
-        idx->cur_vq = pqa ? idx->pqa_vq : 0;
+        const int64_t pvq = pqa ? pb->vq : 0;
+        const uint32_t* exv = pqa ? pb->valid + c0 * pvq : valid;
+        // per query of this chunk: the select's threshold depth (the 960-block second pass brings its own)
+        const int32_t* sel_m = pqs ? pb->m + c0 : nullptr;
+        idx->cur_vq = pvq;
         idx->cur_tq = t_sel;
         idx->cur_pqk = pqk;
         float4* qinfo = idx->qsInfo.as<float4>();
@@ -295,7 +299,7 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
             q8a.prio = idx->q8_prio;
             if (pqk) {  // query q of this chunk: its bitmap row (the exact pass's too)
                 q8a.qmask = exv;
-                q8a.qmask_ld = idx->pqa_vq;
+                q8a.qmask_ld = pvq;
                 q8a.qmask_n = cn;
             }
             // k_q8_blockkey's variant: two blocks per slot (RB8 = 2) run the
@@ -463,7 +467,7 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
 #undef WV_SELF
                 return;
             }
-#define WV_SELR(RV) k_blk_select<RV><<<gw, 256, 0, s>>>(a.key, ldk, nb, (int)cn, k, metric, qinfo_sel, qmax_sel, idx->d_maxn2, gd, gacc_sel, idx->qsCand.as<uint32_t>(), idx->qsNc.as<int32_t>(), flags, idx->qsEps.as<float>(), list, cnt, tA, idx->qsCap.as<float>(), lc, t_sel, pqs ? exv : nullptr, pqs ? idx->pqa_vq : 0, pqs ? idx->pqa_m + c0 : nullptr)
+#define WV_SELR(RV) k_blk_select<RV><<<gw, 256, 0, s>>>(a.key, ldk, nb, (int)cn, k, metric, qinfo_sel, qmax_sel, idx->d_maxn2, gd, gacc_sel, idx->qsCand.as<uint32_t>(), idx->qsNc.as<int32_t>(), flags, idx->qsEps.as<float>(), list, cnt, tA, idx->qsCap.as<float>(), lc, t_sel, pqs ? exv : nullptr, pqs ? pvq : 0, sel_m)
             if (RV == 2) WV_SELR(2); else if (RV == 4) WV_SELR(4); else if (RV == 8) WV_SELR(8); else if (RV == 16) WV_SELR(16);
             else if (RV == 32) WV_SELR(32); else WV_SELR(64);
 #undef WV_SELR
@@ -541,11 +545,9 @@ int search_qs(wv_index* idx, hipStream_t s, int64_t nq, int k, int mode, const u
             HIPCHK(idx->pqaM2.ensure((size_t)(c0 + cn) * sizeof(int32_t)));
             k_fill_u32<<<(unsigned)((cn + 255) / 256), 256, 0, s>>>(idx->pqaM2.as<uint32_t>() + c0, cn, 960u);
             k_flag_list<<<(unsigned)((cn + 255) / 256), 256, 0, s>>>(flags, (int)cn, olist, idx->qscount + 2, 1);
-            const int32_t* keep = idx->pqa_m;
-            idx->pqa_m = idx->pqaM2.as<int32_t>();  // the select reads pqa_m + c0
+            sel_m = idx->pqaM2.as<int32_t>() + c0;  // (sel reads it by reference; the chunk ends with this pass)
             sel(16, olist, idx->qscount + 2, nullptr);
             if (sel_rc) return sel_rc;
-            idx->pqa_m = keep;
             exa(16, olist, idx->qscount + 2);
             HIPCHK(hipGetLastError());
         }

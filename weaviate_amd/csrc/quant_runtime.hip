@@ -303,10 +303,10 @@ int search_bq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
     if (rc) return rc;
     // a multi-allow batch (pqa_run): valid is the union of the
     // queries' bitmaps -- the minima run over it once -- and each query's
-    // replay reads its own bitmap pqa_valid + q * pqa_vq.  k_bq_fast finds its
+    // replay reads its own bitmap pqa_cur->valid + q * vq.  k_bq_fast finds its
     // rows from one shared bitmap, so such a batch goes through the replay.
-    const uint32_t* own = idx->pqa_valid;
-    const int64_t own_vq = own ? idx->pqa_vq : 0;
+    const uint32_t* own = idx->pqa_cur ? idx->pqa_cur->valid : nullptr;
+    const int64_t own_vq = own ? idx->pqa_cur->vq : 0;
     HIPCHK(idx->ascI.ensure((size_t)nq * R * sizeof(uint64_t)));
     HIPCHK(idx->ascD.ensure((size_t)nq * R * sizeof(float)));
     HIPCHK(idx->cn.ensure((size_t)nq * sizeof(int32_t)));
@@ -2066,10 +2066,14 @@ static bool rq8_one_chunk(const wv_index* idx, int64_t nq) { return round_up(nq,
 // replay of the unproven queries reads them (k_rq8_replay<.., PQA>; the
 // distance-matrix replay has no per-query form).  Whatever search_rq would
 // refuse is left to the one-query calls, whose errors the batch then reports.
-bool rq_pqa_route(const wv_index* idx, int64_t nq, int k) {
-    if (!idx->rq_bits || !idx->rq_ready || k <= 0 || idx->rq_serial == 8) return false;
+// rq_pqa_max: the most queries such a launch takes (a multiple of 256; 0: none)
+int64_t rq_pqa_max(const wv_index* idx, int k) {
+    if (!idx->rq_bits || !idx->rq_ready || k <= 0 || idx->rq_serial == 8) return 0;
     const int R = idx->rescore_limit > k ? idx->rescore_limit : k;
-    return R <= 8192 && rq8_route(idx, R) && rq8_one_chunk(idx, nq);
+    return R <= 8192 && rq8_route(idx, R) ? rq8_chunk(idx) : 0;
+}
+bool rq_pqa_route(const wv_index* idx, int64_t nq, int k) {
+    return rq_pqa_max(idx, k) > 0 && rq8_one_chunk(idx, nq);
 }
 
 template <int NC>
@@ -2371,11 +2375,11 @@ int search_rq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
     const bool mfma = rq8_route(idx, R);
     // a multi-allow batch (pqa_run): valid is the union of the
     // queries' bitmaps -- the keys and the select run over it once -- and each
-    // query's candidates and replay read its own bitmap pqa_valid + q * pqa_vq
-    const uint32_t* own = idx->pqa_valid;
-    const int64_t own_vq = own ? idx->pqa_vq : 0;
-    // rq_pqa_route is the one rule: the gate (pqa_shared) asked it under the same
-    // lock before it set pqa_valid, so this never fires for a caller; it holds
+    // query's candidates and replay read its own bitmap pqa_cur->valid + q * vq
+    const uint32_t* own = idx->pqa_cur ? idx->pqa_cur->valid : nullptr;
+    const int64_t own_vq = own ? idx->pqa_cur->vq : 0;
+    // rq_pqa_route is the one rule: the gate (pqa_route, pqa_plan) asked it under the
+    // same lock before pqa_cur was set, so this never fires for a caller; it holds
     // the MFMA route and the one-chunk condition that rq8_candidates and
     // rq8_replay_list below rely on (their own refusals are unreachable past it)
     if (own && !rq_pqa_route(idx, nq, k))

@@ -30,6 +30,7 @@
 #include "../../include/wv_knn.h"
 #include "key_plan.h"
 #include "list_plan.h"
+#include "pqa_plan.h"
 #include "kernels.hip"
 #include "l1_kernels.hip"
 #include "bq_kernels.hip"
@@ -94,6 +95,15 @@ static inline int pq_g16(int m) { return (m + 15) / 16; }
 
 struct wv_batcher;
 static void batcher_free(wv_index* idx, wv_batcher* b);
+
+// the shared launch of a multi-allow batch (pqa_run): what search_qs,
+// search_bq and search_rq read through wv_index::pqa_cur
+struct PqaBatch {
+    const uint32_t* valid;  // device: query q's own bitmap at valid + q * vq
+    int64_t vq;             // words per query bitmap
+    const int32_t* m;       // device, per query: the select's threshold depth (k_blk_select mq)
+    int R;                  // block-key route: 64 (R - 1)-block candidate lists
+};
 
 struct wv_index {
     std::mutex mu;
@@ -276,14 +286,13 @@ struct wv_index {
     DBuf rq8Qp, rq8Qcs, rq8Qm, rq8Fq, rq8Fm;                  // rq-8 MFMA route: query planes, flagged queries
     DBuf rq8M;                                                // a multi-allow batch: the select's threshold M per query
     int rq_mfma = 1;
-    // per-query allow lists (wv_index_search_by_vector_batch_allow): the exact
-    // pass and the replays of search_qs read query q's bitmap at
-    // pqa_valid + q * pqa_vq; cur_vq / cur_tq are set only while search_qs runs
-    // in that mode (the launchers pass them to the kernels)
-    const uint32_t* pqa_valid = nullptr;
-    const int32_t* pqa_m = nullptr;  // per query: the select's threshold depth (k_blk_select mq)
-    int pqa_R = 8;
-    int sel_lower = 0;  // k_blk_select lowers an overflowing threshold instead of flagging                   // the select / exact list size 64 (R - 1) for them
+    // per-query allow lists (wv_index_search_by_vector_batch_multi_allow):
+    // pqa_cur is the shared launch in flight, set by pqa_run for the length of
+    // its search_core call only (the exact pass and the replays of search_qs
+    // read query q's bitmap at valid + q * vq); cur_vq / cur_tq are set only
+    // while search_qs runs in that mode (the launchers pass them to the kernels)
+    const PqaBatch* pqa_cur = nullptr;
+    int sel_lower = 0;  // k_blk_select lowers an overflowing threshold instead of flagging
     int pqa = 1;
     int64_t pqa_budget_mb = 4096;
     int64_t pqa_split_max = 64;
@@ -292,7 +301,6 @@ struct wv_index {
     int pqa_bq = 1;         // option pqa_bq: a BQ index shares the launch too (search_bq: union minima, own replays)
     int pqa_rq = 1;         // option pqa_rq: an rq-8 / rq-1 index as well (search_rq: union keys, own candidates and replays)
     std::atomic<int> batch_rows{1};  // option batch_rows: the batcher's dense lists as slot bitmaps (read by callers)
-    int64_t pqa_vq = 0;
     int64_t cur_vq = 0;
     const float* cur_tq = nullptr;
     bool cur_pqk = false;   // search_qs: this batch's keys are per-query (the replays' upper bounds hold)
@@ -423,6 +431,7 @@ int search_hnsw_lists(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t
                       int32_t* o_n);
 int pq_fit_rows(wv_index* idx, const float* dT, int64_t n, uint64_t seed);
 int64_t bq_max_batch(const wv_index* idx);
+int64_t rq_pqa_max(const wv_index* idx, int k);
 bool rq_pqa_route(const wv_index* idx, int64_t nq, int k);
 int rq_init(wv_index* idx);
 int rq_encode_queries(wv_index* idx, hipStream_t s, int64_t nq);

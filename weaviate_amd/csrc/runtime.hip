@@ -11,7 +11,6 @@
 // cap is a multiple of 128 (the MFMA tile) so tiles never read out of bounds.
 #include "rt_index.h"
 #include <cpuid.h>
-#include <functional>
 #include <map>
 
 // ---------------------------------------------------------------------------
@@ -1059,7 +1058,7 @@ static int search_core(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
         return search_qs(idx, s, nq, k, mode, valid, o_ids, o_d, o_n, o_flags);
     }
     // (BQ and rq took their own searches above; PQ and SQ never come with per-query bitmaps)
-    if (idx->pqa_valid) return set_err(WV_ERR_UNSUPPORTED, "per-query allow lists: block-key route only");
+    if (idx->pqa_cur) return set_err(WV_ERR_UNSUPPORTED, "per-query allow lists: block-key route only");
     const int KP = k + idx->margin;
     const bool mfma_ok = KP <= 32 && metric_bilinear(idx->metric) && !idx->force_replay;
     idx->stats.queries += (uint64_t)nq;
@@ -1495,22 +1494,42 @@ extern "C" int wv_index_search_by_vector_batch(wv_index* idx, const float* queri
 // allow_ids[allow_offsets[q] .. allow_offsets[q+1]) when allow_modes[q] == 1,
 // unfiltered when 0 -- the results of wv_index_search_by_vector_batch called
 // per query (Weaviate's callers each bring their filter: shard_read.go:415-424
-// -> flat/index.go:423-448 with its own helpers.AllowList).  On the block-key
-// route the batch shares one launch: the keys run over the union of the
-// queries' rows, each query's exact pass and replay over its own bitmap
-// (search_qs).  Other routes: the queries grouped by identical list, one batch
-// call per group.
-static int multi_allow_grouped(wv_index* idx, const float* queries, int64_t nq, int64_t d, int32_t k,
-                               const uint64_t* allow_ids, const int64_t* off, const int32_t* modes, uint64_t* out_ids,
-                               float* out_dists, int32_t* out_counts) {
+// -> flat/index.go:423-448 with its own helpers.AllowList).  pqa_plan
+// (pqa_plan.h) decides which rows share a launch -- the keys (or
+// quantized minima) run over the union of the rows' lists, each query's exact
+// pass and replay over its own bitmap -- and which are searched grouped by
+// identical list, one batch call per group; pqa_exec carries the plan out.
+
+// rows qs of a batch as a batch of their own: the queries gathered ...
+static void gather_rows(const float* queries, int64_t d, const std::vector<int64_t>& qs, std::vector<float>& qb) {
+    const size_t dd = (size_t)std::max<int64_t>(d, 0);
+    qb.resize(qs.size() * dd + 1);
+    for (size_t i = 0; i < qs.size(); i++) memcpy(&qb[i * dd], queries + qs[i] * (int64_t)dd, dd * sizeof(float));
+}
+// ... and their results scattered back into the batch's outputs
+static void scatter_rows(const std::vector<int64_t>& qs, int32_t k, const uint64_t* ids, const float* ds,
+                         const int32_t* cnt, uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
+    const int64_t kk = std::max<int32_t>(k, 0);
+    for (size_t i = 0; i < qs.size(); i++) {
+        out_counts[qs[i]] = cnt[i];
+        memcpy(out_ids + qs[i] * kk, ids + (int64_t)i * kk, (size_t)cnt[i] * sizeof(uint64_t));
+        memcpy(out_dists + qs[i] * kk, ds + (int64_t)i * kk, (size_t)cnt[i] * sizeof(float));
+    }
+}
+
+// the batch's rows `rows` grouped by identical list, one batch call per group
+// (takes idx->mu per call)
+static int multi_allow_grouped(wv_index* idx, const float* queries, int64_t d, int32_t k, const uint64_t* allow_ids,
+                               const int64_t* off, const int32_t* modes, const std::vector<int64_t>& rows,
+                               uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
     std::map<std::pair<int, std::string>, std::vector<int64_t>> groups;
-    for (int64_t q = 0; q < nq; q++) {
+    for (int64_t q : rows) {
         std::string key;
         if (modes[q] == 1)
             key.assign(reinterpret_cast<const char*>(allow_ids + off[q]), (size_t)(off[q + 1] - off[q]) * sizeof(uint64_t));
         groups[{modes[q], key}].push_back(q);
     }
-    const int64_t kk = std::max<int32_t>(k, 0), dd = std::max<int64_t>(d, 0);
+    const int64_t kk = std::max<int32_t>(k, 0);
     std::vector<float> qb;
     std::vector<uint64_t> ids;
     std::vector<float> ds;
@@ -1518,233 +1537,97 @@ static int multi_allow_grouped(wv_index* idx, const float* queries, int64_t nq, 
     for (auto& g : groups) {
         const std::vector<int64_t>& qs = g.second;
         const int64_t n = (int64_t)qs.size();
-        qb.resize((size_t)(n * dd) + 1);
+        gather_rows(queries, d, qs, qb);
         ids.resize((size_t)(n * kk) + 1);
         ds.resize((size_t)(n * kk) + 1);
         cnt.resize((size_t)n);
-        for (int64_t i = 0; i < n; i++) memcpy(&qb[(size_t)(i * dd)], queries + qs[i] * dd, (size_t)dd * sizeof(float));
         const int64_t q0 = qs[0];
         int rc = wv_index_search_by_vector_batch(idx, qb.data(), n, d, k, modes[q0] ? allow_ids + off[q0] : nullptr,
                                                  modes[q0] ? off[q0 + 1] - off[q0] : 0, modes[q0], ids.data(),
                                                  ds.data(), cnt.data());
         if (rc) return rc;
-        for (int64_t i = 0; i < n; i++) {
-            out_counts[qs[i]] = cnt[i];
-            memcpy(out_ids + qs[i] * kk, &ids[(size_t)(i * kk)], (size_t)cnt[i] * sizeof(uint64_t));
-            memcpy(out_dists + qs[i] * kk, &ds[(size_t)(i * kk)], (size_t)cnt[i] * sizeof(float));
-        }
+        scatter_rows(qs, k, ids.data(), ds.data(), cnt.data(), out_ids, out_dists, out_counts);
     }
     return WV_OK;
 }
 
-// the indexes whose multi-allow batch shares one launch: the uncompressed
-// block-key route (search_qs) and the quantized flat searches that resolve
-// every query themselves (no flags, no select depths, no per-query keys):
-// under option pqa_bq flat + BQ (search_bq: the block minima over the union,
-// each query's R-heap replay over its own bitmap), under option pqa_rq flat
-// rq-8 / rq-1 on the integer-MFMA route while a launch of nq queries keeps
-// every query's keys (search_rq, rq_pqa_route: union keys, own candidates and
-// replays).  PQ and SQ stay grouped by list.
-static bool pqa_quant_route(const wv_index* idx, int64_t nq, int32_t k) {
-    if (idx->rq_bits) return idx->pqa_rq && rq_pqa_route(idx, nq, k);
-    return idx->compression == WV_COMPRESSION_BQ && idx->pqa_bq;
-}
-// qmax: the queries one launch takes (pqa_budget_mb); a longer batch runs as
-// sub-batches of qmax, and it is their size the rq route's one-chunk rule sees
-static bool pqa_shared(const wv_index* idx, int64_t nq, int64_t d, int32_t k, int64_t qmax) {
-    if (!idx->pqa || nq <= 1 || idx->dims == 0 || d != idx->dims || k <= 0 || idx->npresent <= 0) return false;
-    if (pqa_quant_route(idx, std::min(nq, qmax), k)) return true;
-    return idx->compression == WV_COMPRESSION_NONE && !idx->rq_bits && qs_route(idx, k);
-}
-
-// the select's threshold depth per query (k_blk_select mq): a block key is
-// the minimum over the union's rows, this query's own with probability ~ its
-// share rho of the union, so ~ (k+1) / rho blocks hold its k+1 nearest; twice
-// that (unclamped; unlisted queries: k+1)
-static void pqa_depths(const wv_index* idx, int64_t nq, int32_t k, const int64_t* off, const int32_t* modes,
-                       std::vector<double>& m) {
-    int64_t tot = 0;
-    for (int64_t q = 0; q < nq; q++) tot += modes[q] ? off[q + 1] - off[q] : idx->npresent;
-    const double U = (double)std::max<int64_t>(1, std::min<int64_t>(tot, idx->npresent));
-    m.assign((size_t)nq, (double)(k + 1));
-    for (int64_t q = 0; q < nq; q++)
-        if (modes[q]) m[(size_t)q] = 2.0 * (k + 1) * std::max(1.0, U / (double)std::max<int64_t>(1, off[q + 1] - off[q]));
-}
-
-// the shared block-key launch of a multi-allow batch once the per-query
-// bitmaps (bits, vq words each, ANDed with present) are on the device: union,
-// search_core, results to the host; left = the queries the launch flagged
-// (searched alone by the caller).  Called with idx->mu held.
-static int pqa_run(wv_index* idx, hipStream_t s, const float* queries, int64_t nq, int64_t d, int32_t k, int64_t vq,
-                   uint32_t* bits, uint64_t* out_ids, float* out_dists, int32_t* out_counts,
-                   std::vector<int64_t>& left) {
-    uint32_t* uni = idx->pqaUnion.as<uint32_t>();
-    HIPCHK(hipMemsetAsync(uni, 0, (size_t)std::max<int64_t>(idx->cap / 32, vq) * sizeof(uint32_t), s));
-    k_pqa_union<<<(unsigned)((vq + 255) / 256), 256, 0, s>>>(bits, vq, nq, uni);
-    HIPCHK(hipGetLastError());
-    HIPCHK(idx->qraw.ensure((size_t)nq * d * sizeof(float)));
-    HIPCHK(idx->oIds.ensure((size_t)nq * k * sizeof(uint64_t)));
-    HIPCHK(idx->oD.ensure((size_t)nq * k * sizeof(float)));
-    HIPCHK(idx->oN.ensure((size_t)nq * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(idx->qraw.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, s));
-    idx->stats.last_scan_rows = (uint64_t)idx->hiwater;
-    idx->pqa_valid = bits;
-    idx->pqa_vq = vq;
-    idx->pqa_m = idx->pqaM.as<int32_t>();
-    // the queries the shared launch leaves unresolved (flags) are searched
-    // alone afterwards (a sparse list's own gathered sub-index or window)
-    // instead of by the one-wave replay inside the launch, which walks every
-    // block key of the union for one query (35 ms at 1M rows, 2 % lists)
-    HIPCHK(idx->oF.ensure((size_t)nq * sizeof(int32_t)));
-    // (search_bq and search_rq resolve every query themselves and write no flags)
-    int32_t* dflags = idx->pqa_alone && !pqa_quant_route(idx, nq, k) ? idx->oF.as<int32_t>() : nullptr;
-    int rc = search_core(idx, s, idx->qraw.as<float>(), nq, d, k, 0, uni, idx->npresent, idx->oIds.as<uint64_t>(),
-                         idx->oD.as<float>(), idx->oN.as<int32_t>(), dflags);
-    idx->pqa_valid = nullptr;
-    idx->pqa_vq = 0;
-    idx->pqa_m = nullptr;
-    if (rc) return rc;
-    std::vector<int32_t> hf(dflags ? (size_t)nq : 0);
-    HIPCHK(hipMemcpyAsync(out_ids, idx->oIds.p, (size_t)nq * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(out_dists, idx->oD.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(out_counts, idx->oN.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (dflags) HIPCHK(hipMemcpyAsync(hf.data(), dflags, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int64_t q = 0; q < (int64_t)hf.size(); q++)
-        if (hf[(size_t)q]) left.push_back(q);
-    idx->stats.replayed_queries += (uint64_t)left.size();
-    return WV_OK;
-}
-
-
-static thread_local bool t_pqa_nosplit = false;
-
-extern "C" int wv_index_search_by_vector_batch_multi_allow(wv_index* idx, const float* queries, int64_t nq, int64_t d,
-                                                           int32_t k, const uint64_t* allow_ids,
-                                                           const int64_t* allow_offsets, const int32_t* allow_modes,
-                                                           uint64_t* out_ids, float* out_dists, int32_t* out_counts);
-
-// the queries qs of a multi-allow batch as their own batch -- grouped by list
-// (shared == false: one-query-list calls) or shared (the one-launch path, no
-// further split) -- results scattered back into the batch's outputs
-static int multi_allow_subset(wv_index* idx, const float* queries, int64_t d, int32_t k, const uint64_t* allow_ids,
-                              const int64_t* allow_offsets, const int32_t* allow_modes, const std::vector<int64_t>& qs,
-                              bool shared, uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
-    const int64_t kk = std::max<int32_t>(k, 0);
-    const int64_t n = (int64_t)qs.size();
-    std::vector<float> qb((size_t)(n * d) + 1);
-    std::vector<int64_t> off((size_t)n + 1, 0);
-    std::vector<int32_t> modes((size_t)n);
-    std::vector<uint64_t> aid;
-    for (int64_t i = 0; i < n; i++) {
-        const int64_t q = qs[(size_t)i];
-        memcpy(&qb[(size_t)(i * d)], queries + q * d, (size_t)d * sizeof(float));
-        modes[(size_t)i] = allow_modes[q];
-        if (allow_modes[q]) aid.insert(aid.end(), allow_ids + allow_offsets[q], allow_ids + allow_offsets[q + 1]);
-        off[(size_t)i + 1] = (int64_t)aid.size();
+// what the index offers a multi-allow batch (mu held).  A launch is shared on
+// the uncompressed block-key route (search_qs) and by the quantized flat
+// searches that resolve every query themselves (no flags, no select depths,
+// no per-query keys): under option pqa_bq flat + BQ (search_bq: the block
+// minima over the union, each query's R-heap replay over its own bitmap),
+// under option pqa_rq flat rq-8 / rq-1 on the integer-MFMA route while a launch
+// keeps every query's keys (search_rq, rq_pqa_max: union keys, own candidates
+// and replays).  PQ and SQ stay grouped by list.
+static PqaRoute pqa_route(const wv_index* idx, int64_t d, int32_t k) {
+    PqaRoute r{false, false, false, 0};
+    if (!idx->pqa || idx->dims == 0 || d != idx->dims || k <= 0 || idx->npresent <= 0) return r;
+    if (idx->rq_bits) {
+        r.quant_max = idx->pqa_rq ? rq_pqa_max(idx, k) : 0;
+        r.shared = r.quant_max > 0;
+    } else if (idx->compression == WV_COMPRESSION_BQ) {
+        r.quant_max = INT64_MAX;
+        r.shared = idx->pqa_bq != 0;
+    } else if (idx->compression == WV_COMPRESSION_NONE && qs_route(idx, k)) {
+        r.shared = r.keyed = true;
+        r.own_keys = pqa_keys_route(idx);  // (per-query keys serve sparse lists in the launch)
     }
-    aid.push_back(0);  // a valid pointer when every list is empty
-    std::vector<uint64_t> oi((size_t)(n * kk) + 1);
-    std::vector<float> od((size_t)(n * kk) + 1);
-    std::vector<int32_t> oc((size_t)n);
-    int rc;
-    if (!shared) {
-        rc = multi_allow_grouped(idx, qb.data(), n, d, k, aid.data(), off.data(), modes.data(), oi.data(), od.data(),
-                                 oc.data());
-    } else {
-        t_pqa_nosplit = true;
-        rc = wv_index_search_by_vector_batch_multi_allow(idx, qb.data(), n, d, k, aid.data(), off.data(), modes.data(),
-                                                         oi.data(), od.data(), oc.data());
-        t_pqa_nosplit = false;
-    }
-    if (rc) return rc;
-    for (int64_t i = 0; i < n; i++) {
-        const int64_t q = qs[(size_t)i];
-        out_counts[q] = oc[(size_t)i];
-        memcpy(out_ids + q * kk, &oi[(size_t)(i * kk)], (size_t)oc[(size_t)i] * sizeof(uint64_t));
-        memcpy(out_dists + q * kk, &od[(size_t)(i * kk)], (size_t)oc[(size_t)i] * sizeof(float));
-    }
-    return WV_OK;
+    return r;
 }
 
-extern "C" int wv_index_search_by_vector_batch_multi_allow(wv_index* idx, const float* queries, int64_t nq, int64_t d,
-                                                           int32_t k, const uint64_t* allow_ids,
-                                                           const int64_t* allow_offsets, const int32_t* allow_modes,
-                                                           uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
-    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
-    if (nq < 0) return set_err(WV_ERR_INVALID, "negative batch");
-    if (nq == 0) return WV_OK;
-    if (!allow_offsets || !allow_modes || !out_counts || (d > 0 && !queries))
-        return set_err(WV_ERR_INVALID, "nil argument");
+// a multi-allow batch's lists in the caller's form
+enum PqaForm { PQA_IDS, PQA_BITS, PQA_ROWS };
+struct PqaLists {
+    PqaForm form;
+    const int32_t* modes;
+    const uint64_t* ids;  // PQA_IDS: row q's list ids[off[q] .. off[q + 1])
+    const int64_t* off;
+    const uint32_t* bits;  // PQA_BITS: row q's doc-id bitmap bits + q * words
+    int64_t words;
+    const wv_batch_row* rows;  // PQA_ROWS: the batcher's slot bitmaps
+};
+
+// bitmap forms -> id lists (absolute doc ids) of the rows in want (all rows:
+// nullptr), for the paths that take lists
+static void pqa_to_lists(const PqaLists& in, int64_t nq, uint64_t id_base, const std::vector<int64_t>* want,
+                         std::vector<uint64_t>& ids, std::vector<int64_t>& off) {
+    std::vector<char> w((size_t)nq, want ? 0 : 1);
+    if (want)
+        for (int64_t q : *want) w[(size_t)q] = 1;
+    ids.clear();
+    off.assign((size_t)nq + 1, 0);
     for (int64_t q = 0; q < nq; q++) {
-        if (allow_modes[q] != 0 && allow_modes[q] != 1) return set_err(WV_ERR_INVALID, "allow mode %d", allow_modes[q]);
-        if (allow_offsets[q] < 0 || allow_offsets[q + 1] < allow_offsets[q])
-            return set_err(WV_ERR_INVALID, "allow offsets not ascending at %lld", (long long)q);
-        if (allow_modes[q] == 1 && allow_offsets[q + 1] > allow_offsets[q] && !allow_ids)
-            return set_err(WV_ERR_INVALID, "nil allow ids");
-    }
-    std::unique_lock<std::mutex> g(idx->mu);
-    const int64_t vq = round_up(std::max<int64_t>(idx->hiwater, 1), 256) / 32;  // words per query bitmap
-    const int64_t qmax = std::max<int64_t>(1, (idx->pqa_budget_mb << 20) / (vq * (int64_t)sizeof(uint32_t)));
-    const bool fast = pqa_shared(idx, nq, d, k, qmax);
-    const bool keyed = fast && !pqa_quant_route(idx, std::min(nq, qmax), k);  // the block-key select's depths and split
-    if (!fast) {
-        g.unlock();
-        return multi_allow_grouped(idx, queries, nq, d, k, allow_ids, allow_offsets, allow_modes, out_ids, out_dists,
-                                   out_counts);
-    }
-    std::vector<double> md((size_t)nq, 0.0);
-    if (keyed) pqa_depths(idx, nq, k, allow_offsets, allow_modes, md);
-    if (keyed && !t_pqa_nosplit && !pqa_keys_route(idx)) {  // (per-query keys serve sparse lists in the launch)
-        // lists too sparse for the union's keys (deeper than the 960-block
-        // lists) would end in the one-wave replay, a walk over every block
-        // key: a few of them go as their own searches instead (an allow list
-        // that sparse takes the gathered sub-index route)
-        std::vector<int64_t> sp, dn;
-        for (int64_t q = 0; q < nq; q++) (md[(size_t)q] > 960.0 ? sp : dn).push_back(q);
-        if (!sp.empty() && (int64_t)sp.size() <= idx->pqa_split_max && !dn.empty()) {
-            g.unlock();
-            int rc = multi_allow_subset(idx, queries, d, k, allow_ids, allow_offsets, allow_modes, sp, false, out_ids,
-                                        out_dists, out_counts);
-            if (rc) return rc;
-            return multi_allow_subset(idx, queries, d, k, allow_ids, allow_offsets, allow_modes, dn, true, out_ids,
-                                      out_dists, out_counts);
+        if (in.modes[q] && w[(size_t)q]) {
+            const bool rows = in.form == PQA_ROWS;
+            const uint32_t* b = rows ? in.rows[q].host : in.bits + q * in.words;
+            const int64_t nw = rows ? in.rows[q].words : in.words;
+            for (int64_t i = 0; i < nw; i++)
+                for (uint32_t v = b[i]; v; v &= v - 1)
+                    ids.push_back((rows ? id_base : 0) + (uint64_t)(i * 32 + __builtin_ctz(v)));
         }
+        off[(size_t)q + 1] = (int64_t)ids.size();
     }
-    if (nq > qmax) {  // bitmaps past the budget: consecutive sub-batches
-        g.unlock();
-        for (int64_t q0 = 0; q0 < nq; q0 += qmax) {
-            const int64_t n = std::min(qmax, nq - q0);
-            int rc = wv_index_search_by_vector_batch_multi_allow(idx, queries + q0 * d, n, d, k, allow_ids,
-                                                                 allow_offsets + q0, allow_modes + q0,
-                                                                 out_ids + q0 * k, out_dists + q0 * k, out_counts + q0);
-            if (rc) return rc;
-        }
-        return WV_OK;
-    }
-    HIPCHK(hipSetDevice(idx->device));
-    hipStream_t s = idx->stream;
-    // the unlisted queries take the present bitmap; the ids of all lists go
-    // over as given (one copy), their queries found on the device
-    std::vector<int32_t> q0list;
+    ids.push_back(0);  // a valid pointer when every list is empty
+}
+
+// the fills: the device bitmaps (vq words each, ANDed with present) of the nq
+// queries of one launch, from the caller's form of their lists.
+// Id lists: the unlisted queries take the present bitmap; the ids of all lists
+// go over as given (one copy), their queries found on the device (q0list: host
+// scratch of the caller's that the copy reads until the launch has synchronized)
+static int pqa_fill_ids(wv_index* idx, hipStream_t s, int64_t vq, int64_t nq, const uint64_t* allow_ids,
+                        const int64_t* allow_offsets, const int32_t* allow_modes, std::vector<int32_t>& q0list,
+                        uint32_t* bits) {
+    q0list.clear();
     for (int64_t q = 0; q < nq; q++)
         if (allow_modes[q] == 0) q0list.push_back((int32_t)q);
     const int64_t nids = allow_offsets[nq] - allow_offsets[0];
-    HIPCHK(idx->pqaBits.ensure((size_t)(nq * vq) * sizeof(uint32_t)));
-    HIPCHK(idx->pqaUnion.ensure((size_t)std::max<int64_t>(idx->cap / 32, vq) * sizeof(uint32_t)));
     // pqaQ: [nq + 1] offsets (int64), [nq] modes, [n0] unlisted queries
     HIPCHK(idx->pqaQ.ensure((size_t)(nq + 1) * sizeof(int64_t) + (size_t)(2 * nq + 2) * sizeof(int32_t)));
     HIPCHK(idx->pqaIds.ensure((size_t)(nids + 1) * sizeof(uint64_t)));
-    std::vector<int32_t> hm((size_t)nq);
-    for (int64_t q = 0; q < nq; q++) hm[(size_t)q] = (int32_t)std::min(960.0, std::ceil(md[(size_t)q]));
-    // 448-block lists, 960 when a query wants more (k_blk_exact<16>)
-    idx->pqa_R = *std::max_element(hm.begin(), hm.end()) > 448 ? 16 : 8;
-    HIPCHK(idx->pqaM.ensure((size_t)nq * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(idx->pqaM.p, hm.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
     int64_t* d_off = idx->pqaQ.as<int64_t>();
     int32_t* d_modes = reinterpret_cast<int32_t*>(d_off + nq + 1);
     int32_t* d_q0 = d_modes + nq + 1;
-    uint32_t* bits = idx->pqaBits.as<uint32_t>();
     HIPCHK(hipMemsetAsync(bits, 0, (size_t)(nq * vq) * sizeof(uint32_t), s));
     HIPCHK(hipMemcpyAsync(d_off, allow_offsets, (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_modes, allow_modes, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -1762,88 +1645,233 @@ extern "C" int wv_index_search_by_vector_batch_multi_allow(wv_index* idx, const 
                                                                   idx->id_base, idx->hiwater, idx->present, vq, bits);
         HIPCHK(hipGetLastError());
     }
-    std::vector<int64_t> left;
-    int rc = pqa_run(idx, s, queries, nq, d, k, vq, bits, out_ids, out_dists, out_counts, left);
-    if (rc || left.empty()) return rc;
-    g.unlock();
-    return multi_allow_subset(idx, queries, d, k, allow_ids, allow_offsets, allow_modes, left, false, out_ids, out_dists,
-                              out_counts);
+    return WV_OK;
 }
 
-// bitmap allow lists -> id lists (absolute doc ids), for the paths that take lists
-static void bits_to_lists(const uint32_t* bits, int64_t words, const int32_t* modes, int64_t nq,
-                          std::vector<uint64_t>& ids, std::vector<int64_t>& off, const std::vector<char>* want) {
-    ids.clear();
-    off.assign((size_t)nq + 1, 0);
-    for (int64_t q = 0; q < nq; q++) {
-        if (modes[q] && (!want || (*want)[(size_t)q]))
-            for (int64_t w = 0; w < words; w++)
-                for (uint32_t v = bits[q * words + w]; v; v &= v - 1)
-                    ids.push_back((uint64_t)(w * 32 + __builtin_ctz(v)));
-        off[(size_t)q + 1] = (int64_t)ids.size();
-    }
-    ids.push_back(0);
-}
-
-// The shared multi-allow launch from per-query bitmaps, whatever their host
-// form: off = the lists' size prefix sums (the select depths), fill writes the
-// per-query device bitmaps (vq words each, ANDed with present), lists gives
-// the same lists as ids (the paths that take id lists: a batch the shared
-// launch does not serve, a split of too-sparse lists, the flagged queries).
-// Called with g holding idx->mu; returns with it released or held.
-typedef std::function<int(hipStream_t, int64_t, uint32_t*, const int32_t*)> PqaFill;
-typedef std::function<void(std::vector<uint64_t>&, std::vector<int64_t>&, const std::vector<char>*)> PqaLists;
-static int pqa_bitmap_core(wv_index* idx, std::unique_lock<std::mutex>& g, const float* queries, int64_t nq, int64_t d,
-                           int32_t k, const int32_t* allow_modes, const std::vector<int64_t>& off, const PqaFill& fill,
-                           const PqaLists& lists, uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
-    auto by_lists = [&](const std::vector<int64_t>* qs) -> int {
-        g.unlock();
-        std::vector<uint64_t> ids;
-        std::vector<int64_t> lo;
-        std::vector<char> want;  // the flagged queries' lists only
-        if (qs) {
-            want.assign((size_t)nq, 0);
-            for (int64_t q : *qs) want[(size_t)q] = 1;
-        }
-        lists(ids, lo, qs ? &want : nullptr);
-        if (!qs)
-            return wv_index_search_by_vector_batch_multi_allow(idx, queries, nq, d, k, ids.data(), lo.data(),
-                                                               allow_modes, out_ids, out_dists, out_counts);
-        return multi_allow_subset(idx, queries, d, k, ids.data(), lo.data(), allow_modes, *qs, false, out_ids, out_dists,
-                                  out_counts);
-    };
-    const int64_t vq = round_up(std::max<int64_t>(idx->hiwater, 1), 256) / 32;
-    const int64_t qmax = std::max<int64_t>(1, (idx->pqa_budget_mb << 20) / (vq * (int64_t)sizeof(uint32_t) * 2));
-    const bool fast = pqa_shared(idx, nq, d, k, qmax) && nq <= qmax;
-    const bool keyed = fast && !pqa_quant_route(idx, nq, k);  // the block-key select's depths and split
-    std::vector<double> md((size_t)nq, 0.0);
-    if (keyed) pqa_depths(idx, nq, k, off.data(), allow_modes, md);
-    bool split = false;
-    if (keyed && !pqa_keys_route(idx)) {  // the id-list call's split of too-sparse lists (see there)
-        int64_t nsp = 0;
-        for (int64_t q = 0; q < nq; q++) nsp += md[(size_t)q] > 960.0;
-        split = nsp > 0 && nsp <= idx->pqa_split_max && nsp < nq;
-    }
-    if (!fast || split) return by_lists(nullptr);
-    HIPCHK(hipSetDevice(idx->device));
-    hipStream_t s = idx->stream;
-    std::vector<int32_t> hm((size_t)nq);
-    for (int64_t q = 0; q < nq; q++) hm[(size_t)q] = (int32_t)std::min(960.0, std::ceil(md[(size_t)q]));
-    idx->pqa_R = *std::max_element(hm.begin(), hm.end()) > 448 ? 16 : 8;
-    HIPCHK(idx->pqaM.ensure((size_t)nq * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(idx->pqaM.p, hm.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(idx->pqaBits.ensure((size_t)(nq * vq) * sizeof(uint32_t)));
-    HIPCHK(idx->pqaUnion.ensure((size_t)std::max<int64_t>(idx->cap / 32, vq) * sizeof(uint32_t)));
+static int pqa_upload_modes(wv_index* idx, hipStream_t s, int64_t nq, const int32_t* allow_modes) {
     HIPCHK(idx->pqaQ.ensure((size_t)(nq + 1) * sizeof(int32_t)));
-    int32_t* d_modes = idx->pqaQ.as<int32_t>();
-    HIPCHK(hipMemcpyAsync(d_modes, allow_modes, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(idx->pqaQ.p, allow_modes, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    return WV_OK;
+}
+
+// Dense doc-id bitmaps: the callers' words from doc id id_base & ~31 on, one
+// strided copy (pqaIds holds them), then the shift by id_base & 31 on the device
+static int pqa_fill_bits(wv_index* idx, hipStream_t s, int64_t vq, int64_t nq, const uint32_t* allow_bits,
+                         int64_t words, const int32_t* allow_modes, uint32_t* bits) {
+    int rc = pqa_upload_modes(idx, s, nq, allow_modes);
+    if (rc) return rc;
+    const int64_t sw = vq + 1;  // the slot window plus the shift's spill word
+    const int64_t b0 = (int64_t)(idx->id_base >> 5);
+    const int64_t avail = std::max<int64_t>(0, std::min<int64_t>(sw, words - b0));
+    HIPCHK(idx->pqaIds.ensure((size_t)(nq * sw) * sizeof(uint32_t) + 8));
+    uint32_t* raw = reinterpret_cast<uint32_t*>(idx->pqaIds.p);
+    if (avail > 0)
+        HIPCHK(hipMemcpy2DAsync(raw, (size_t)sw * sizeof(uint32_t), allow_bits + b0, (size_t)words * sizeof(uint32_t),
+                                (size_t)avail * sizeof(uint32_t), (size_t)nq, hipMemcpyHostToDevice, s));
+    k_pqa_from_bits<<<(unsigned)std::min<int64_t>((nq * vq + 255) / 256, 8192), 256, 0, s>>>(
+        raw, sw, avail, idx->pqaQ.as<int32_t>(), nq, (int)(idx->id_base & 31), idx->present, vq, bits);
+    HIPCHK(hipGetLastError());
+    return WV_OK;
+}
+
+// The batcher's rows: page-locked host memory the kernel reads in place
+static int pqa_fill_rows(wv_index* idx, hipStream_t s, int64_t vq, int64_t nq, const wv_batch_row* rows,
+                         const int32_t* allow_modes, uint32_t* bits) {
+    int rc = pqa_upload_modes(idx, s, nq, allow_modes);
+    if (rc) return rc;
+    HIPCHK(idx->pqaIds.ensure((size_t)nq * sizeof(wv_batch_row)));
+    HIPCHK(hipMemcpyAsync(idx->pqaIds.p, rows, (size_t)nq * sizeof(wv_batch_row), hipMemcpyHostToDevice, s));
+    k_pqa_from_rows<<<(unsigned)std::min<int64_t>((nq * vq + 255) / 256, 8192), 256, 0, s>>>(
+        reinterpret_cast<const wv_batch_row*>(idx->pqaIds.p), idx->pqaQ.as<int32_t>(), nq, idx->present, vq, bits);
+    HIPCHK(hipGetLastError());
+    return WV_OK;
+}
+
+// the shared launch of nq queries once their bitmaps (bits, vq words each) and
+// their select depths (pqaM) are on the device: union, search_core, results to
+// the host; left = the queries the launch flagged.  Called with idx->mu held.
+static int pqa_run(wv_index* idx, hipStream_t s, const float* queries, int64_t nq, int64_t d, int32_t k, int64_t vq,
+                   const uint32_t* bits, int R, bool flags, uint64_t* out_ids, float* out_dists,
+                   int32_t* out_counts, std::vector<int64_t>& left) {
+    HIPCHK(idx->pqaUnion.ensure((size_t)std::max<int64_t>(idx->cap / 32, vq) * sizeof(uint32_t)));
+    uint32_t* uni = idx->pqaUnion.as<uint32_t>();
+    HIPCHK(hipMemsetAsync(uni, 0, (size_t)std::max<int64_t>(idx->cap / 32, vq) * sizeof(uint32_t), s));
+    k_pqa_union<<<(unsigned)((vq + 255) / 256), 256, 0, s>>>(bits, vq, nq, uni);
+    HIPCHK(hipGetLastError());
+    HIPCHK(idx->qraw.ensure((size_t)nq * d * sizeof(float)));
+    HIPCHK(idx->oIds.ensure((size_t)nq * k * sizeof(uint64_t)));
+    HIPCHK(idx->oD.ensure((size_t)nq * k * sizeof(float)));
+    HIPCHK(idx->oN.ensure((size_t)nq * sizeof(int32_t)));
+    HIPCHK(idx->oF.ensure((size_t)nq * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(idx->qraw.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, s));
+    idx->stats.last_scan_rows = (uint64_t)idx->hiwater;
+    // the queries a keyed launch leaves unresolved (flags) are searched alone
+    // afterwards (a sparse list's own gathered sub-index or window) instead of
+    // by the one-wave replay inside the launch, which walks every block key of
+    // the union for one query (35 ms at 1M rows, 2 % lists)
+    // (search_bq and search_rq resolve every query themselves and write no flags)
+    int32_t* dflags = flags ? idx->oF.as<int32_t>() : nullptr;
+    const PqaBatch cur{bits, vq, idx->pqaM.as<int32_t>(), R};
+    int rc;
+    {
+        struct Scope {  // search_qs / search_bq / search_rq read idx->pqa_cur; no return leaves it set
+            wv_index* i;
+            ~Scope() { i->pqa_cur = nullptr; }
+        } scope{idx};
+        idx->pqa_cur = &cur;
+        rc = search_core(idx, s, idx->qraw.as<float>(), nq, d, k, 0, uni, idx->npresent, idx->oIds.as<uint64_t>(),
+                         idx->oD.as<float>(), idx->oN.as<int32_t>(), dflags);
+    }
+    if (rc) return rc;
+    std::vector<int32_t> hf(dflags ? (size_t)nq : 0);
+    HIPCHK(hipMemcpyAsync(out_ids, idx->oIds.p, (size_t)nq * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_dists, idx->oD.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_counts, idx->oN.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (dflags) HIPCHK(hipMemcpyAsync(hf.data(), dflags, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int64_t q = 0; q < (int64_t)hf.size(); q++)
+        if (hf[(size_t)q]) {
+            left.push_back(q);
+            out_counts[q] = 0;  // k_blk_exact flags before it writes a count: nothing of this row is valid yet
+        }
+    idx->stats.replayed_queries += (uint64_t)left.size();
+    return WV_OK;
+}
+
+// one launch step of the plan (mu held): the step's rows as a batch -- in
+// place when they are consecutive, gathered otherwise (the dense half of a
+// split: id lists only) -- filled from `in`, run, and the flagged rows added
+// to alone under their batch row
+static int pqa_step(wv_index* idx, hipStream_t s, const PqaLists& in, const PqaStep& st, bool keyed,
+                    const float* queries, int64_t d, int32_t k, int64_t vq, uint64_t* out_ids, float* out_dists,
+                    int32_t* out_counts, std::vector<int64_t>& alone) {
+    const int64_t n = (int64_t)st.q.size(), q0 = st.q[0];
+    const bool inplace = st.q.back() - q0 + 1 == n;  // (rows ascend)
+    if (!inplace && in.form != PQA_IDS) return set_err(WV_ERR_INVALID, "multi-allow plan: a gathered bitmap launch");
+    HIPCHK(idx->pqaBits.ensure((size_t)(n * vq) * sizeof(uint32_t)));
     uint32_t* bits = idx->pqaBits.as<uint32_t>();
-    int rc = fill(s, vq, bits, d_modes);
+    // the select depths go first: a small pageable copy issued behind the lists' copy and the fill
+    // kernels would hold the host until they are done
+    HIPCHK(idx->pqaM.ensure((size_t)n * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(idx->pqaM.p, st.m.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    std::vector<float> qb;
+    std::vector<uint64_t> aid, oi;
+    std::vector<int64_t> off;
+    std::vector<int32_t> modes, oc, q0list;  // (host memory of asynchronous copies: alive until pqa_run has synchronized)
+    std::vector<float> od;
+    int rc;
+    if (inplace) {
+        queries += q0 * d;
+        if (in.form == PQA_IDS) rc = pqa_fill_ids(idx, s, vq, n, in.ids, in.off + q0, in.modes + q0, q0list, bits);
+        else if (in.form == PQA_BITS) rc = pqa_fill_bits(idx, s, vq, n, in.bits + q0 * in.words, in.words, in.modes + q0, bits);
+        else rc = pqa_fill_rows(idx, s, vq, n, in.rows + q0, in.modes + q0, bits);
+    } else {
+        gather_rows(queries, d, st.q, qb);
+        queries = qb.data();
+        off.assign((size_t)n + 1, 0);
+        modes.resize((size_t)n);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t q = st.q[(size_t)i];
+            modes[(size_t)i] = in.modes[q];
+            if (in.modes[q]) aid.insert(aid.end(), in.ids + in.off[q], in.ids + in.off[q + 1]);
+            off[(size_t)i + 1] = (int64_t)aid.size();
+        }
+        aid.push_back(0);  // a valid pointer when every list is empty
+        oi.resize((size_t)(n * k));
+        od.resize((size_t)(n * k));
+        oc.resize((size_t)n);
+        rc = pqa_fill_ids(idx, s, vq, n, aid.data(), off.data(), modes.data(), q0list, bits);
+    }
     if (rc) return rc;
     std::vector<int64_t> left;
-    rc = pqa_run(idx, s, queries, nq, d, k, vq, bits, out_ids, out_dists, out_counts, left);
-    if (rc || left.empty()) return rc;
-    return by_lists(&left);
+    rc = pqa_run(idx, s, queries, n, d, k, vq, bits, st.R, keyed && idx->pqa_alone,
+                 inplace ? out_ids + q0 * k : oi.data(), inplace ? out_dists + q0 * k : od.data(),
+                 inplace ? out_counts + q0 : oc.data(), left);
+    if (rc) return rc;
+    if (!inplace) scatter_rows(st.q, k, oi.data(), od.data(), oc.data(), out_ids, out_dists, out_counts);
+    for (int64_t i : left) alone.push_back(st.q[(size_t)i]);
+    return WV_OK;
+}
+
+// A multi-allow batch, whatever the form of its lists (sizes[q]: row q's list
+// size): one hold of idx->mu for the plan and all its launches -- the depths
+// and the bitmap width are those of the index the launches see -- then the
+// rows the plan groups and the rows the launches flagged in one grouped pass.
+// (A bitmap form whose launches go through id lists gives the lock up once,
+// before any launch, to convert them.)
+static int pqa_exec(wv_index* idx, const float* queries, int64_t nq, int64_t d, int32_t k, PqaLists in,
+                    const std::vector<int64_t>& sizes, uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
+    std::vector<uint64_t> lids;  // a bitmap form's lists as ids
+    std::vector<int64_t> loff, alone;
+    const PqaLists orig = in;
+    for (std::unique_lock<std::mutex> g(idx->mu);;) {
+        const int64_t vq = round_up(std::max<int64_t>(idx->hiwater, 1), 256) / 32;  // words per query bitmap
+        // the queries one launch takes (pqa_budget_mb); a bitmap form stages the callers' words as well
+        const int64_t qmax = std::max<int64_t>(1, (idx->pqa_budget_mb << 20) / (vq * (int64_t)sizeof(uint32_t)));
+        const int64_t qmax_bits =
+            std::max<int64_t>(1, (idx->pqa_budget_mb << 20) / (vq * (int64_t)sizeof(uint32_t) * 2));
+        const PqaRoute route = pqa_route(idx, d, k);
+        const PqaPlan plan = pqa_plan(nq, k, idx->npresent, in.modes, sizes.data(), qmax, in.form == PQA_IDS ? 0 : qmax_bits,
+                                      idx->pqa_split_max, route);
+        bool launches = false;
+        for (const PqaStep& st : plan.steps) launches |= st.launch;
+        if (launches && in.form != PQA_IDS && plan.via_lists) {
+            // every bitmap as an id list, a host scan that does not need the index: off the lock, and
+            // the batch, now in the id-list form, is planned again under the hold that runs it
+            g.unlock();
+            pqa_to_lists(orig, nq, idx->id_base0, nullptr, lids, loff);
+            in = PqaLists{PQA_IDS, orig.modes, lids.data(), loff.data(), nullptr, 0, nullptr};
+            g.lock();
+            continue;
+        }
+        if (launches) HIPCHK(hipSetDevice(idx->device));
+        for (const PqaStep& st : plan.steps) {
+            if (!st.launch) {
+                alone.insert(alone.end(), st.q.begin(), st.q.end());
+                continue;
+            }
+            int rc = pqa_step(idx, idx->stream, in, st, route.keyed, queries, d, k, vq, out_ids, out_dists, out_counts,
+                              alone);
+            if (rc) return rc;
+        }
+        break;
+    }
+    if (alone.empty()) return WV_OK;
+    if (in.form != PQA_IDS) {  // the lists of the rows searched alone only
+        pqa_to_lists(orig, nq, idx->id_base0, &alone, lids, loff);
+        in = PqaLists{PQA_IDS, orig.modes, lids.data(), loff.data(), nullptr, 0, nullptr};
+    }
+    std::sort(alone.begin(), alone.end());
+    return multi_allow_grouped(idx, queries, d, k, in.ids, in.off, in.modes, alone, out_ids, out_dists, out_counts);
+}
+
+static int pqa_check_args(const wv_index* idx, const float* queries, int64_t nq, int64_t d, const int32_t* allow_modes,
+                          const int32_t* out_counts) {
+    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
+    if (nq < 0) return set_err(WV_ERR_INVALID, "negative batch");
+    if (nq > 0 && (!allow_modes || !out_counts || (d > 0 && !queries))) return set_err(WV_ERR_INVALID, "nil argument");
+    for (int64_t q = 0; q < nq; q++)
+        if (allow_modes[q] != 0 && allow_modes[q] != 1) return set_err(WV_ERR_INVALID, "allow mode %d", allow_modes[q]);
+    return WV_OK;
+}
+
+extern "C" int wv_index_search_by_vector_batch_multi_allow(wv_index* idx, const float* queries, int64_t nq, int64_t d,
+                                                           int32_t k, const uint64_t* allow_ids,
+                                                           const int64_t* allow_offsets, const int32_t* allow_modes,
+                                                           uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
+    int rc = pqa_check_args(idx, queries, nq, d, allow_modes, out_counts);
+    if (rc || nq == 0) return rc;
+    if (!allow_offsets) return set_err(WV_ERR_INVALID, "nil argument");
+    std::vector<int64_t> sizes((size_t)nq);
+    for (int64_t q = 0; q < nq; q++) {
+        if (allow_offsets[q] < 0 || allow_offsets[q + 1] < allow_offsets[q])
+            return set_err(WV_ERR_INVALID, "allow offsets not ascending at %lld", (long long)q);
+        if (allow_modes[q] == 1 && allow_offsets[q + 1] > allow_offsets[q] && !allow_ids)
+            return set_err(WV_ERR_INVALID, "nil allow ids");
+        sizes[(size_t)q] = allow_offsets[q + 1] - allow_offsets[q];
+    }
+    return pqa_exec(idx, queries, nq, d, k, PqaLists{PQA_IDS, allow_modes, allow_ids, allow_offsets, nullptr, 0, nullptr},
+                    sizes, out_ids, out_dists, out_counts);
 }
 
 extern "C" int wv_index_search_by_vector_batch_multi_allow_bitmap(wv_index* idx, const float* queries, int64_t nq,
@@ -1851,46 +1879,18 @@ extern "C" int wv_index_search_by_vector_batch_multi_allow_bitmap(wv_index* idx,
                                                                   int64_t words, const int32_t* allow_modes,
                                                                   uint64_t* out_ids, float* out_dists,
                                                                   int32_t* out_counts) {
-    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
-    if (nq < 0) return set_err(WV_ERR_INVALID, "negative batch");
-    if (nq == 0) return WV_OK;
+    int rc = pqa_check_args(idx, queries, nq, d, allow_modes, out_counts);
+    if (rc || nq == 0) return rc;
     if (words < 0) return set_err(WV_ERR_INVALID, "negative bitmap words");
-    if (!allow_modes || !out_counts || (d > 0 && !queries)) return set_err(WV_ERR_INVALID, "nil argument");
-    bool listed = false;
-    for (int64_t q = 0; q < nq; q++) {
-        if (allow_modes[q] != 0 && allow_modes[q] != 1) return set_err(WV_ERR_INVALID, "allow mode %d", allow_modes[q]);
-        listed |= allow_modes[q] == 1;
-    }
-    if (listed && words > 0 && !allow_bits) return set_err(WV_ERR_INVALID, "nil allow bitmap");
     // list sizes (the select depths) from the bitmaps
-    std::vector<int64_t> off((size_t)nq + 1, 0);
+    std::vector<int64_t> sizes((size_t)nq, 0);
     for (int64_t q = 0; q < nq; q++) {
-        int64_t c = 0;
-        if (allow_modes[q])
-            for (int64_t w = 0; w < words; w++) c += __builtin_popcount(allow_bits[q * words + w]);
-        off[(size_t)q + 1] = off[(size_t)q] + c;
+        if (!allow_modes[q]) continue;
+        if (words > 0 && !allow_bits) return set_err(WV_ERR_INVALID, "nil allow bitmap");
+        for (int64_t w = 0; w < words; w++) sizes[(size_t)q] += __builtin_popcount(allow_bits[q * words + w]);
     }
-    std::unique_lock<std::mutex> g(idx->mu);
-    // the callers' words from doc id id_base & ~31 on, one strided copy (pqaIds
-    // holds them), then the shift by id_base & 31 on the device
-    PqaFill fill = [&](hipStream_t s, int64_t vq, uint32_t* bits, const int32_t* d_modes) -> int {
-        const int64_t sw = vq + 1;  // the slot window plus the shift's spill word
-        const int64_t b0 = (int64_t)(idx->id_base >> 5);
-        const int64_t avail = std::max<int64_t>(0, std::min<int64_t>(sw, words - b0));
-        HIPCHK(idx->pqaIds.ensure((size_t)(nq * sw) * sizeof(uint32_t) + 8));
-        uint32_t* raw = reinterpret_cast<uint32_t*>(idx->pqaIds.p);
-        if (avail > 0)
-            HIPCHK(hipMemcpy2DAsync(raw, (size_t)sw * sizeof(uint32_t), allow_bits + b0, (size_t)words * sizeof(uint32_t),
-                                    (size_t)avail * sizeof(uint32_t), (size_t)nq, hipMemcpyHostToDevice, s));
-        k_pqa_from_bits<<<(unsigned)std::min<int64_t>((nq * vq + 255) / 256, 8192), 256, 0, s>>>(
-            raw, sw, avail, d_modes, nq, (int)(idx->id_base & 31), idx->present, vq, bits);
-        HIPCHK(hipGetLastError());
-        return WV_OK;
-    };
-    PqaLists lists = [&](std::vector<uint64_t>& ids, std::vector<int64_t>& lo, const std::vector<char>* want) {
-        bits_to_lists(allow_bits, words, allow_modes, nq, ids, lo, want);
-    };
-    return pqa_bitmap_core(idx, g, queries, nq, d, k, allow_modes, off, fill, lists, out_ids, out_dists, out_counts);
+    return pqa_exec(idx, queries, nq, d, k, PqaLists{PQA_BITS, allow_modes, nullptr, nullptr, allow_bits, words, nullptr},
+                    sizes, out_ids, out_dists, out_counts);
 }
 
 // The micro-batcher's filtered requests as slot bitmaps (batcher.hip): row q
@@ -1899,32 +1899,11 @@ extern "C" int wv_index_search_by_vector_batch_multi_allow_bitmap(wv_index* idx,
 static int batch_search_slot_bitmaps(wv_index* idx, const float* queries, int64_t nq, int64_t d, int32_t k,
                                      const wv_batch_row* rows, uint64_t* out_ids, float* out_dists,
                                      int32_t* out_counts) {
-    std::vector<int32_t> modes((size_t)nq, 1);
-    std::vector<int64_t> off((size_t)nq + 1, 0);
-    for (int64_t q = 0; q < nq; q++) off[(size_t)q + 1] = off[(size_t)q] + std::max<int64_t>(rows[q].n, 0);
-
-    std::unique_lock<std::mutex> g(idx->mu);
-    PqaFill fill = [&](hipStream_t s, int64_t vq, uint32_t* bits, const int32_t* d_modes) -> int {
-        HIPCHK(idx->pqaIds.ensure((size_t)nq * sizeof(wv_batch_row)));
-        HIPCHK(hipMemcpyAsync(idx->pqaIds.p, rows, (size_t)nq * sizeof(wv_batch_row), hipMemcpyHostToDevice, s));
-        k_pqa_from_rows<<<(unsigned)std::min<int64_t>((nq * vq + 255) / 256, 8192), 256, 0, s>>>(
-            reinterpret_cast<const wv_batch_row*>(idx->pqaIds.p), d_modes, nq, idx->present, vq, bits);
-        HIPCHK(hipGetLastError());
-        return WV_OK;
-    };
-    PqaLists lists = [&](std::vector<uint64_t>& ids, std::vector<int64_t>& lo, const std::vector<char>* want) {
-        ids.clear();
-        lo.assign((size_t)nq + 1, 0);
-        for (int64_t q = 0; q < nq; q++) {
-            if (!want || (*want)[(size_t)q])
-                for (int64_t w = 0; w < rows[q].words; w++)
-                    for (uint32_t v = rows[q].host[w]; v; v &= v - 1)
-                        ids.push_back(idx->id_base + (uint64_t)(w * 32 + __builtin_ctz(v)));
-            lo[(size_t)q + 1] = (int64_t)ids.size();
-        }
-        ids.push_back(0);
-    };
-    return pqa_bitmap_core(idx, g, queries, nq, d, k, modes.data(), off, fill, lists, out_ids, out_dists, out_counts);
+    const std::vector<int32_t> modes((size_t)nq, 1);
+    std::vector<int64_t> sizes((size_t)nq);
+    for (int64_t q = 0; q < nq; q++) sizes[(size_t)q] = std::max<int64_t>(rows[q].n, 0);
+    return pqa_exec(idx, queries, nq, d, k, PqaLists{PQA_ROWS, modes.data(), nullptr, nullptr, nullptr, 0, rows}, sizes,
+                    out_ids, out_dists, out_counts);
 }
 
 // every query of the batch under its own list ids[lo[q] .. hi[q]), in list
