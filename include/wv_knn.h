@@ -628,6 +628,7 @@ typedef struct wv_stats {
 #define WV_ROUTE_RQ8_INT8 10 /* flat rq-8: k_rq8_keys (exact rq-8 block minima on the integer MFMA) */
 #define WV_ROUTE_L1_TILE 11  /* manhattan: k_l1_rows (register-tiled exact L1 of every row, then the heap replay) */
 #define WV_ROUTE_LIST_SCAN 12 /* hnsw flat search in list order: k_list_dist + k_list_heap over the allow lists' entries */
+#define WV_ROUTE_BQ_PACKED 13 /* BQ block minima: k_bq_packmin (integer MFMA over the packed codes, <= 64 words) */
 int wv_index_stats(wv_index *idx, wv_stats *out);
 
 /* Diagnostic hook (tests): the last MFMA batch's candidates [nq][KP]:
@@ -655,6 +656,11 @@ int wv_index_debug_bqmin(wv_index *idx, int64_t q, float *mins, int64_t *nblk, i
  * 6 = HBM-streaming GEMV, 3 = f32 MFMA select; other values are rejected),
  * "replay_par" (flagged-query replay form, default 2), "rp_few" (device-counted
  * replay lists up to this long take the one-launch 8-wave form, default 16),
+ * "bq_pack" (BQ block minima from the packed codes on the integer MFMA,
+ * k_bq_packmin, codes of up to 64 words = 4096 dims: 1 = always, 0 = never,
+ * -1 = auto, the default: codes of 25-64 words where "bq8" = 1; WV_ROUTE_BQ_PACKED,
+ * DESIGN.md §3.5d; "bq8" chooses between the stored +-1 plane and the VALU
+ * kernels wherever this route is not taken),
  * "bq_fast" (1 = BQ queries whose rescored result no hamming tie can change
  * skip the R-heap replay, k_bq_fast; default 0: slower on C4),
  * "exact_bm" / "exact_cap"

@@ -185,6 +185,9 @@ __global__ __launch_bounds__(256, 2) void k_bq_blockmin_lds(const uint64_t* __re
 // (its own valid words are its occupancy), so a sparse list inside a dense
 // union does not walk every block of the union while its heap is short.
 // A template parameter: the other instantiations compile as before.
+// NW = 64 with BLK = 32: codes of 33-64 words under 32-row minima (the packed
+// route, bq_packed.hip) -- the same block walk and insertions, the query code
+// in LDS and the popcounts accumulated in chunks of words.
 template <int NW, bool REC, int BLK = BQBLK, bool PQA = false>
 __global__ __launch_bounds__(64) void k_bq_replay(const uint64_t* __restrict__ codes, int64_t ccap, int words,
                                                   const uint32_t* __restrict__ valid, int64_t nslots,
@@ -217,7 +220,139 @@ __global__ __launch_bounds__(64) void k_bq_replay(const uint64_t* __restrict__ c
         if (REC) rec_n[li] = 0;
     }
     __syncthreads();
-    if constexpr (BLK == 32 && NW > 0) {
+    if constexpr (BLK == 32 && NW > 32) {
+        // 32-row blocks, 33-64 code words (the packed route's minima).  The block
+        // walk is the arm's below (the same windows and next_blk, repeated here so
+        // that arm compiles as before); 6 NW registers of codes do not fit, so
+        // the query code sits in LDS (uniform reads) and a pair's popcounts
+        // accumulate over the words in chunks of WCH, the next chunk's loads in
+        // flight.  The pair after this one is chosen under the top before the
+        // insertions (a superset, as below) and its first chunk and valid word
+        // load while lane 0 inserts.
+        // the block minima in windows of 16 chunks of 64 blocks: the next window
+        // loads while this one is scanned (16 loads in flight instead of one
+        // chunk ahead), and a chunk with no block under the top when its window
+        // came up is never looked at again (the top only falls once the heap is full)
+        float bw[16], bn[16];
+        auto load_win = [&](float* dst, int64_t base) {
+#pragma unroll
+            for (int u = 0; u < 16; u++) {
+                const int64_t b = base + u * 64 + lane;
+                if constexpr (PQA) dst[u] = (b < nblk && valid[b] != 0u) ? Bq[b] : __builtin_inff();
+                else dst[u] = b < nblk ? Bq[b] : __builtin_inff();
+            }
+        };
+        auto win_mask = [&]() -> uint32_t {
+            const int len = *s_len;
+            const float top = len > 0 ? hr[0].d : 0.f;
+            uint32_t m = 0;
+#pragma unroll
+            for (int u = 0; u < 16; u++)
+                if (__ballot(bw[u] != __builtin_inff() && (len < R || top > bw[u]))) m |= 1u << u;
+            return m;
+        };
+        int64_t wb0 = 0;
+        load_win(bw, 0);
+        load_win(bn, 1024);
+        uint32_t wm = win_mask();
+        int wi = -1;
+        float bmc = __builtin_inff();
+        uint64_t cmask = 0;
+        auto next_blk = [&]() -> int64_t {
+            const int len = *s_len;
+            const float top = len > 0 ? hr[0].d : 0.f;
+            while (true) {
+                while (cmask) {
+                    const int j = __builtin_ctzll(cmask);
+                    cmask &= cmask - 1;
+                    if (len < R || top > __shfl(bmc, j)) return wb0 + wi * 64 + j;
+                }
+                if (wi >= 0) wm &= ~((2u << wi) - 1u);
+                if (wm) {
+                    wi = __builtin_ctz(wm);
+                    float v = bw[0];
+#pragma unroll
+                    for (int u = 1; u < 16; u++) v = wi == u ? bw[u] : v;
+                    bmc = v;
+                    cmask = __ballot(bmc != __builtin_inff() && (len < R || top > bmc));
+                    continue;
+                }
+                wb0 += 1024;
+                if (wb0 >= nblk) return -1;
+#pragma unroll
+                for (int u = 0; u < 16; u++) bw[u] = bn[u];
+                load_win(bn, wb0 + 1024);
+                wm = win_mask();
+                wi = -1;
+            }
+        };
+        constexpr int WCH = 8;
+        __shared__ uint64_t s_q[NW];
+        if (lane < NW) s_q[lane] = lane < words ? qc[(int64_t)lane * ldq] : 0ull;
+        __syncthreads();
+        auto load_chunk = [&](uint64_t (&x)[WCH], int w0, int64_t srow, bool in) {
+#pragma unroll
+            for (int i = 0; i < WCH; i++) x[i] = (in && w0 + i < words) ? codes[(int64_t)(w0 + i) * ccap + srow] : 0ull;
+        };
+        auto first = [&](uint64_t (&x)[WCH], uint32_t& vword, int64_t pa, int64_t pb) {
+            const int64_t blk = lane < 32 ? pa : pb;
+            const int64_t srow = blk * 32 + (lane & 31);
+            vword = blk >= 0 ? valid[blk] : 0u;
+            load_chunk(x, 0, srow, blk >= 0 && srow < nslots);
+        };
+        uint64_t x0[WCH];
+        uint32_t vword = 0;
+        int64_t pa = next_blk();
+        int64_t pb = pa >= 0 ? next_blk() : -1;
+        if (pa >= 0) first(x0, vword, pa, pb);
+        while (pa >= 0) {
+            const int64_t blk = lane < 32 ? pa : pb;
+            const int64_t srow = blk * 32 + (lane & 31);
+            const bool in = blk >= 0 && srow < nslots;
+            const bool ok = in && ((vword >> (lane & 31)) & 1u);
+            uint32_t h = 0;
+            uint64_t x[WCH], y[WCH];
+#pragma unroll
+            for (int i = 0; i < WCH; i++) x[i] = x0[i];
+            for (int w0 = 0; w0 < words; w0 += WCH) {
+                load_chunk(y, w0 + WCH, srow, in);  // words past the code load as 0
+#pragma unroll
+                for (int i = 0; i < WCH; i++) h += (uint32_t)__popcll(x[i] ^ s_q[w0 + i]);
+#pragma unroll
+                for (int i = 0; i < WCH; i++) x[i] = y[i];
+            }
+            const float dist = (float)h;
+            const int64_t na = next_blk();
+            const int64_t nb = na >= 0 ? next_blk() : -1;
+            if (na >= 0) first(x0, vword, na, nb);  // in flight during the insertions below
+            const int len = *s_len;
+            const float top = len > 0 ? hr[0].d : 0.f;
+            uint64_t mask = __ballot(ok && (len < R || top > dist));
+            if (mask) {
+                s_d[lane] = dist;
+                __syncthreads();
+                if (lane == 0) {
+                    PHeap hp{hr, *s_len};
+                    while (mask) {  // block pa's rows (lanes 0-31), then pb's (32-63): id order
+                        const int jj = __builtin_ctzll(mask);
+                        mask &= mask - 1;
+                        const float dj = s_d[jj];
+                        const uint64_t sj = id_base + (uint64_t)((jj < 32 ? pa : pb) * 32 + (jj & 31));
+                        const bool ins = ph_offer(hp, R, sj, dj);
+                        if (REC && ins) {
+                            const int c = rec_n[li];
+                            if (c < cap) { rec_ids[(int64_t)li * cap + c] = sj; rec_d[(int64_t)li * cap + c] = dj; }
+                            rec_n[li] = c < cap ? c + 1 : cap + 1;
+                        }
+                    }
+                    *s_len = hp.len;
+                }
+                __syncthreads();
+            }
+            pa = na;
+            pb = nb;
+        }
+    } else if constexpr (BLK == 32 && NW > 0) {
         // 32-row blocks, software-pipelined: the codes of the next two visitable
         // blocks (chosen under the top before the current insertions: a superset,
         // a block that stops qualifying only offers rows ph_offer rejects) load

@@ -4,10 +4,25 @@
 // (see rt_index.h for the unit split).
 #include "rt_index.h"
 
-static bool bq8_route(const wv_index* idx) { return idx->bq8 != nullptr && idx->bq8_opt && idx->bq_kernel != 1; }
-// rows per block minimum of the route: 32 on the integer MFMA (the block count
-// rounded to whole ring slots: two blocks per slot up to 768 bits), 256 otherwise
-static int64_t bq_blk(const wv_index* idx) { return bq8_route(idx) ? 32 : BQBLK; }
+// Option bq_pack: the block minima from the packed codes (k_bq_packmin,
+// bq_packed.hip), codes of up to 64 words.  1 = at every such width, whatever
+// bq8 says; -1 (auto) = the width classes the measurements of DESIGN §3.5d
+// admit (25-32 and 33-64 words), and only where bq8 = 1 asks for matrix-core minima.
+// bq_kernel = 1 (the generic kernels) wins over both.
+static bool bq_pack_auto(int words) {
+    return (BQ_PACK_AUTO_25_32 && words >= 25 && words <= 32) || (BQ_PACK_AUTO_33_64 && words >= 33 && words <= 64);
+}
+static bool bq_pack_route(const wv_index* idx) {
+    if (idx->bq_pack == 0 || idx->bq_kernel == 1 || idx->words < 1 || idx->words > 64) return false;
+    return idx->bq_pack == 1 || (idx->bq8_opt && bq_pack_auto(idx->words));
+}
+static bool bq8_route(const wv_index* idx) {
+    return !bq_pack_route(idx) && idx->bq8 != nullptr && idx->bq8_opt && idx->bq_kernel != 1;
+}
+// rows per block minimum of the route: 32 on the integer MFMA (the stored-plane
+// route's block count rounded to whole ring slots: two blocks per slot up to
+// 768 bits), 256 otherwise
+static int64_t bq_blk(const wv_index* idx) { return bq_pack_route(idx) || bq8_route(idx) ? 32 : BQBLK; }
 static int64_t bq_nblk(const wv_index* idx) {
     const int64_t nb = std::max<int64_t>((idx->hiwater + bq_blk(idx) - 1) / bq_blk(idx), 1);
     return bq8_route(idx) && idx->dpb8b <= 768 ? round_up(nb, 2) : nb;
@@ -100,11 +115,13 @@ static int bq_blockmin_i8(wv_index* idx, hipStream_t s, const uint32_t* valid, i
 }
 
 // compile-time word count for the LDS-broadcast block-minima kernel and the
-// replay's unrolled loads (words <= 32, i.e. d <= 2048); 0 = generic kernels
+// replay's unrolled loads (words <= 32, i.e. d <= 2048); 64 = the 32-row
+// replay's chunked arm (33-64 words under the packed route's minima);
+// 0 = generic kernels
 static int bq_nw(wv_index* idx) {
     const int words = idx->words;
     const int nw = words <= 2 ? 2 : words <= 4 ? 4 : words <= 8 ? 8 : words <= 12 ? 12 : words <= 16 ? 16
-                 : words <= 24 ? 24 : words <= 32 ? 32 : 0;
+                 : words <= 24 ? 24 : words <= 32 ? 32 : (words <= 64 && bq_blk(idx) == 32) ? 64 : 0;
     return idx->bq_kernel == 1 ? 0 : nw;
 }
 
@@ -121,6 +138,14 @@ static int bq_blockmin(wv_index* idx, hipStream_t s, const uint32_t* valid, int6
     if (idx->timing && g0 == 0) HIPCHK(hipEventRecord(idx->ev0, s));
     const uint64_t* qc = idx->qcodes.as<uint64_t>();
     float* bm = idx->bqmin.as<float>();
+    if (bq_pack_route(idx)) {
+        const hipError_t e = (hipError_t)wv_bq_packmin(s, idx->codes, idx->cap, words, valid, nslots, qc, nq,
+                                                       qlist + g0, F, nblk, bm);
+        if (e != hipSuccess) return set_err(WV_ERR_HIP, "k_bq_packmin: %s", hipGetErrorString(e));
+        if (idx->timing && g0 == 0) HIPCHK(hipEventRecord(idx->ev1, s));
+        idx->stats.last_route = WV_ROUTE_BQ_PACKED;
+        return WV_OK;
+    }
     if (bq8_route(idx)) {
         int rc = bq_blockmin_i8(idx, s, valid, g0, F, nblk, bm);
         if (rc) return rc;
@@ -192,7 +217,9 @@ static int bq_replay(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_
     } while (0)
 #define WV_RPR(NWV, RECV, PQV)                                     \
     do {                                                           \
-        if constexpr (NWV > 0) {                                   \
+        if constexpr (NWV > 32) {                                  \
+            WV_RPB(NWV, RECV, 32, PQV);                            \
+        } else if constexpr (NWV > 0) {                            \
             if (b32) WV_RPB(NWV, RECV, 32, PQV);                   \
             else WV_RPB(NWV, RECV, BQBLK, PQV);                    \
         } else {                                                   \
@@ -213,6 +240,7 @@ static int bq_replay(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_
     case 16: WV_RP(16); break;
     case 24: WV_RP(24); break;
     case 32: WV_RP(32); break;
+    case 64: WV_RP(64); break;
     default: WV_RP(0); break;
     }
 #undef WV_RPR
@@ -229,7 +257,8 @@ static bool bq_fast(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_t
                     int32_t* out_n, int32_t* skip, int* rc) {
     *rc = WV_OK;
     const int nw = bq_nw(idx);
-    if (!idx->bq_fast || bq_blk(idx) != 32 || k > BQF_K || !metric_bilinear(idx->metric) ||
+    // the packed route's minima (block count not rounded to ring slots) keep to the replay
+    if (!idx->bq_fast || bq_pack_route(idx) || bq_blk(idx) != 32 || k > BQF_K || !metric_bilinear(idx->metric) ||
         (nw != 8 && nw != 12 && nw != 16 && nw != 24))
         return false;
     const bool v5 = idx->variant == WV_VARIANT_AVX512;

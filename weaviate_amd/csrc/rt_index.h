@@ -52,6 +52,12 @@ using namespace wv;
 // ---------------------------------------------------------------------------
 int set_err(int code, const char* fmt, ...);
 
+// bq_packed.hip: 32-row BQ block minima from the packed codes (a hipError_t)
+int wv_bq_packmin(hipStream_t s, const uint64_t* codes, int64_t ccap, int words, const uint32_t* valid, int64_t nslots,
+                  const uint64_t* qcodes, int64_t ldq, const int32_t* qlist, int nlist, int64_t nblk, float* bmin);
+// the width classes (code words) option bq_pack = -1 sends there: DESIGN §3.5d
+constexpr bool BQ_PACK_AUTO_25_32 = true, BQ_PACK_AUTO_33_64 = true;
+
 #define HIPCHK(x)                                                                              \
     do {                                                                                       \
         hipError_t e_ = (x);                                                                   \
@@ -139,6 +145,7 @@ struct wv_index {
     unsigned char* bq8 = nullptr;
     int dpb8b = 0;
     int bq8_opt = 1;             // option bq8: block minima from the +-1 plane (1) or the VALU kernels (0)
+    int bq_pack = -1;            // option bq_pack: block minima from the packed codes (1), never (0), auto (-1)
     int64_t bq_last_nq = 0, bq_last_nblk = 0, bq_last_blk = 256;  // debug hook (wv_index_debug_bqmin): the last BQ batch's first group
     int scan_window = 1;         // option scan_window: an allow list scans only [allow.Min, allow.Max]
     // gathered allow-list search: a sparse allow list's rows (ascending id) as

@@ -784,6 +784,10 @@ extern "C" int wv_index_set_option(wv_index* idx, const char* key, int64_t value
         idx->q8_shape = (int)value;
     }
     else if (k == "bq8") idx->bq8_opt = value ? 1 : 0;      // BQ block minima on the integer MFMA (1) or VALU (0)
+    else if (k == "bq_pack") {  // BQ block minima from the packed codes: 1 always (<= 64 words), 0 never, -1 auto
+        if (value < -1 || value > 1) return set_err(WV_ERR_INVALID, "bq_pack must be -1, 0 or 1");
+        idx->bq_pack = (int)value;
+    }
     else if (k == "pqa") idx->pqa = value ? 1 : 0;
     else if (k == "sel_lower") idx->sel_lower = value ? 1 : 0;  // per-query allow lists share one block-key launch
     else if (k == "pqa_alone") idx->pqa_alone = value ? 1 : 0;  // unresolved per-query lists searched alone
