@@ -167,7 +167,8 @@ int wv_index_search_by_vector_batch(wv_index *idx, const float *queries, int64_t
  * over the lists' union, each query's candidates and -- where they do not
  * prove its R-list -- its R-heap replay over its own bitmap; 0, the
  * distance-matrix route ("rq_mfma" 0, rq-1 without its +-1 plane, more than
- * 1024 rotated dims, a rescore limit past the candidate lists) and a batch
+ * 1024 rotated dims unless "rq_wide" takes them, more than 4096, a rescore
+ * limit past the candidate lists) and a batch
  * whose keys pass 4 GiB run one rq search per distinct list. */
 int wv_index_search_by_vector_batch_multi_allow(wv_index *idx, const float *queries, int64_t nq, int64_t d,
                                                 int32_t k, const uint64_t *allow_ids, const int64_t *allow_offsets,
@@ -661,6 +662,9 @@ int wv_index_debug_bqmin(wv_index *idx, int64_t q, float *mins, int64_t *nblk, i
  * -1 = auto, the default: codes of 25-64 words where "bq8" = 1; WV_ROUTE_BQ_PACKED,
  * DESIGN.md §3.5d; "bq8" chooses between the stored +-1 plane and the VALU
  * kernels wherever this route is not taken),
+ * "rq_wide" (flat rq-8 / rq-1 above 1024 rotated dims, up to 4096, on the
+ * integer-MFMA route, k_rq8_keys_cp: 1 = always, 0 = never (the
+ * distance-matrix route), -1 = auto, the default: rq-1 only),
  * "bq_fast" (1 = BQ queries whose rescored result no hamming tie can change
  * skip the R-heap replay, k_bq_fast; default 0: slower on C4),
  * "exact_bm" / "exact_cap"

@@ -2075,11 +2075,14 @@ int rq_dist(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_t q0, int
 }
 
 // rq-8 / rq-1 on the integer matrix cores (rq8_mfma.hip): the query
-// fragments stay in VGPRs up to D = 1024; the candidate lists hold R + 2
-// entries; rq-1 needs its +-1 plane
+// fragments stay in VGPRs up to D = 1024 (k_rq8_keys) and, in column parts, up
+// to D = 4096 (k_rq8_keys_cp, option rq_wide); the candidate
+// lists hold R + 2 entries; rq-1 needs its +-1 plane
 static bool rq8_route(const wv_index* idx, int R) {
-    return (idx->rq_bits == 8 || (idx->rq_bits == 1 && idx->rq1_pm)) && idx->rq_mfma && idx->rq_D <= 1024 &&
-           qs_R(R + 1) != 0 && idx->hiwater > 0;
+    const bool width = idx->rq_D <= 1024 ||
+                       (idx->rq_D <= 4096 && (idx->rq_wide == 1 || (idx->rq_wide < 0 && rq_wide_auto(idx->rq_bits))));
+    return (idx->rq_bits == 8 || (idx->rq_bits == 1 && idx->rq1_pm)) && idx->rq_mfma && width && qs_R(R + 1) != 0 &&
+           idx->hiwater > 0;
 }
 
 // query chunks of rq8_candidates: key rows of at most 4 GiB
@@ -2169,6 +2172,8 @@ static int rq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const
     a.fl2 = fl2;
     a.fcos = fcos;
     a.dbg_serial = idx->rq_serial;
+    a.nc = NC;
+    const int QG = NC > 16 ? rq8_wide_queries(NC) : 256;  // queries per workgroup (both divide the padding)
     idx->rq_dbg_nq = std::min<int64_t>(QC, nq);
     idx->rq_dbg_nb = nblk;
     for (int64_t c0 = 0; c0 < nq; c0 += QC) {
@@ -2177,7 +2182,7 @@ static int rq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const
         a.Qp = Qp + c0 * D;
         a.qmeta = Qm + c0;
         a.qcsum = Qcs + c0;
-        a.nqg = (int)(cpad / 256);
+        a.nqg = (int)(cpad / QG);
         // spans: ~2048 workgroups (8 per CU), at least 16 blocks each
         int64_t nspans = std::max<int64_t>(1, std::min<int64_t>(nblk / 16, (2048 + a.nqg - 1) / a.nqg));
         const int64_t bps = (nblk + nspans - 1) / nspans;
@@ -2187,7 +2192,8 @@ static int rq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const
         const unsigned grid = (unsigned)(a.nqg * nspans);
         const bool time_it = idx->timing && c0 == 0;
         if (time_it) HIPCHK(hipEventRecord(idx->ev0, s));
-        switch (NC) {
+        if (NC > 16) HIPCHK((hipError_t)wv_rq8_keys_wide(a, s, bits));
+        else switch (NC) {
         case 1: launch_rq8_keys<1>(a, grid, s, bits); break;
         case 2: launch_rq8_keys<2>(a, grid, s, bits); break;
         case 3: launch_rq8_keys<3>(a, grid, s, bits); break;

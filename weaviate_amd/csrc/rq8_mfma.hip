@@ -15,6 +15,8 @@
 //               block, reduced in registers to the block minimum (a NaN
 //               distance -> -inf: its block is always a candidate and the
 //               query is replayed)
+//               (k_rq8_keys_cp: the same keys for 1024 < D <= 4096, the block
+//               streamed in column parts; instantiated in rq8_wide.hip)
 //   k_rq8_sel   wave per query: M = the (R+1)-th smallest block minimum;
 //               candidates = every block with minimum <= M -- they hold every
 //               row with distance < M and at least R+1 rows <= M
@@ -43,9 +45,10 @@ struct RQ8Args {
     int64_t nblk;                // 32-row blocks to scan
     int blocks_per_span;
     int nspans;
-    int nqg;                     // query groups of 256
+    int nqg;                     // query groups of 256 (k_rq8_keys_cp: of 128 / 64)
     float fl2, fcos;             // L2: 1, 0; cosine: 0, 1; dot: 0, 0 (rq_dist's)
     int dbg_serial;              // debug option rq_serial: one block in flight, drained before each barrier
+    int nc;                      // k_rq8_keys_cp: 64-column chunks per row (D / 64)
 };
 
 namespace {
@@ -116,6 +119,194 @@ __host__ __device__ constexpr int rq8_nbuf(int NC) {
 }
 
 // ---------------------------------------------------------------------------
+// rq8_block_min<BITS, NQ>: the epilogue of a 32-row block, shared by k_rq8_keys
+// (NQ = 2 query tiles per wave) and k_rq8_keys_cp (NQ = 1).  acc[m][n][r] is
+// the integer sum of row 16m + 4g + r (g = lane >> 4) and query 16n +
+// (lane & 15); the block's meta (32 x 16 B), code sums (32 x 4 B) and valid
+// word are in LDS at mb / cb / vb.  out[n] = the minimum over the block's 32
+// rows of the reference's distance for query 16n + (lane & 15), in every lane
+// (-inf when a valid row's distance is NaN).  The float expression is the
+// reference's, in its order, unfused; V is NQ floats wide, so the fast forms
+// are element-wise either way (NQ = 2: v_pk_mul_f32 / v_pk_add_f32, each
+// element rounded as the scalar op would).
+// ---------------------------------------------------------------------------
+template <int NQ>
+struct rq8_fv {
+    typedef float T __attribute__((ext_vector_type(NQ)));
+};
+template <int BITS, int NQ>
+__device__ __forceinline__ void rq8_block_min(const i32x4_t (&acc)[2][NQ], unsigned mb0, unsigned cb0, unsigned vb,
+                                              const float4 (&ym)[NQ], bool qfine, int D, float fl2, float fcos,
+                                              int dbg, int lane, float (&out)[NQ]) {
+    typedef typename rq8_fv<NQ>::T V;
+    constexpr float FINE = 1e16f;
+    const int g = lane >> 4;
+    const float fD = (float)D;
+    const float s_ = 1.0f + fl2;
+    const bool l2 = fl2 != 0.f;
+    // the lane's rows 16m + 4g + r: meta, code sums; the block's valid word
+    i32x4_t mt[2][4], cs[2];
+    const unsigned mb = mb0 + (unsigned)(g * 64);
+    mt[0][0] = lds_ld16_o<0>(mb);
+    mt[0][1] = lds_ld16_o<16>(mb);
+    mt[0][2] = lds_ld16_o<32>(mb);
+    mt[0][3] = lds_ld16_o<48>(mb);
+    mt[1][0] = lds_ld16_o<256>(mb);
+    mt[1][1] = lds_ld16_o<272>(mb);
+    mt[1][2] = lds_ld16_o<288>(mb);
+    mt[1][3] = lds_ld16_o<304>(mb);
+    const unsigned cb = cb0 + (unsigned)(g * 16);
+    cs[0] = lds_ld16_o<0>(cb);
+    cs[1] = lds_ld16_o<64>(cb);
+    uint32_t vw0 = rq8_lds_ld4(vb);
+    qs_wait_lgkm<0>();
+    // the loaded registers are defined only after the wait: tie them to it,
+    // or the compiler may schedule their uses above it
+    asm volatile("" : "+v"(mt[0][0]), "+v"(mt[0][1]), "+v"(mt[0][2]), "+v"(mt[0][3]), "+v"(vw0));
+    asm volatile("" : "+v"(mt[1][0]), "+v"(mt[1][1]), "+v"(mt[1][2]), "+v"(mt[1][3]));
+    asm volatile("" : "+v"(cs[0]), "+v"(cs[1]));
+    const uint32_t vw = __builtin_amdgcn_readfirstlane(vw0);
+    if (dbg & 8) {  // timing: no epilogue math
+        out[0] = __int_as_float(acc[0][0][0] ^ acc[1][NQ - 1][3] ^ mt[0][0][0] ^ cs[1][0]);
+#pragma unroll
+        for (int n = 1; n < NQ; n++) out[n] = out[0];
+        return;
+    }
+    float p[NQ];
+    bool bad[NQ];
+#pragma unroll
+    for (int n = 0; n < NQ; n++) {
+        p[n] = __builtin_inff();
+        bad[n] = false;
+    }
+    // the fast forms: every row valid, every norm <= FINE (wave-uniform);
+    // l2: (1 (n2x + n2y) + 0) - 2 est, cosine / dot: (0 (..) + fcos) - 1 est
+    bool fine = qfine;
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) fine = fine && __int_as_float(mt[m][r][BITS == 8 ? 3 : 1]) <= FINE;
+    const int mode = (vw == 0xFFFFFFFFu && __all(fine) && !(dbg & 4)) ? (l2 ? 0 : 1) : 2;
+    if (mode != 2 && !(dbg & 32)) {
+        // the fast forms, NQ queries of a row per operation.  cosine / dot:
+        // fl(fcos - est) falls as est grows, so the block's minimum is fcos -
+        // (the maximum est) and the subtraction moves out of the row loop.
+        V yx, yz, yyv, ynv, best;
+#pragma unroll
+        for (int n = 0; n < NQ; n++) {
+            yx[n] = ym[n].x;
+            yz[n] = ym[n].z;
+            yyv[n] = BITS == 8 ? ym[n].y : ym[n].x;
+            ynv[n] = BITS == 8 ? ym[n].w : ym[n].y;
+            best[n] = mode == 0 ? __builtin_inff() : -__builtin_inff();
+        }
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                V est;
+                float xnorm;
+                if constexpr (BITS == 8) {
+                    const float xl = __int_as_float(mt[m][r][0]);
+                    const float xs = __int_as_float(mt[m][r][1]);
+                    const float xz = __int_as_float(mt[m][r][2]);
+                    xnorm = __int_as_float(mt[m][r][3]);
+                    const float a1 = fD * xl;
+                    const int kx = (int)(128u * (uint32_t)cs[m][r]) - 16384 * D;
+                    V dotv;
+#pragma unroll
+                    for (int n = 0; n < NQ; n++) dotv[n] = (float)(uint32_t)(acc[m][n][r] + kx);
+                    const V e1 = V(a1) * yx;
+                    const V e2 = V(xl) * yz;
+                    const V e3 = yx * V(xz);
+                    V e4 = V(xs) * yyv;
+                    e4 = e4 * dotv;
+                    est = ((e1 + e2) + e3) + e4;
+                } else {
+                    const float xs = __int_as_float(mt[m][r][0]);
+                    xnorm = __int_as_float(mt[m][r][1]);
+                    V accv;
+#pragma unroll
+                    for (int n = 0; n < NQ; n++) accv[n] = (float)acc[m][n][r];
+                    est = (yyv * V(xs)) * accv;
+                }
+                if (mode == 0) {
+                    const V v = (V(xnorm) + ynv) - V(2.0f) * est;
+#pragma unroll
+                    for (int n = 0; n < NQ; n++) best[n] = fminf(best[n], v[n]);
+                } else {
+#pragma unroll
+                    for (int n = 0; n < NQ; n++) best[n] = fmaxf(best[n], est[n]);
+                }
+            }
+#pragma unroll
+        for (int n = 0; n < NQ; n++) p[n] = mode == 1 ? fcos - best[n] : best[n];
+    } else
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const bool ok = (vw >> (16 * m + 4 * g + r)) & 1u;
+                float est[NQ], xnorm;
+                if constexpr (BITS == 8) {
+                    // est = ((D lx ly + lx cy) + ly cx) + sx sy dot (the reference's order)
+                    const float xl = __int_as_float(mt[m][r][0]);
+                    const float xs = __int_as_float(mt[m][r][1]);
+                    const float xz = __int_as_float(mt[m][r][2]);
+                    xnorm = __int_as_float(mt[m][r][3]);
+                    const float a1 = fD * xl;
+                    const int kx = (int)(128u * (uint32_t)cs[m][r]) - 16384 * D;
+#pragma unroll
+                    for (int n = 0; n < NQ; n++) {
+                        const uint32_t dot = (uint32_t)(acc[m][n][r] + kx);
+                        float e1 = a1 * ym[n].x;
+                        const float e2 = xl * ym[n].z;
+                        const float e3 = ym[n].x * xz;
+                        float e4 = xs * ym[n].y;
+                        e4 = e4 * (float)dot;
+                        float e = e1 + e2;
+                        e = e + e3;
+                        est[n] = e + e4;
+                    }
+                } else {
+                    // rq-1 (BinaryRQDistancer.Distance, binary_rotational_quantization.go:364-385):
+                    // acc = sum s_x w_q = 31 qdim - sum_p 2^(p+1) popcount(x ^ plane_p) exactly
+                    const float xs = __int_as_float(mt[m][r][0]);
+                    xnorm = __int_as_float(mt[m][r][1]);
+#pragma unroll
+                    for (int n = 0; n < NQ; n++) {
+                        const float e = ym[n].x * xs;
+                        est[n] = e * (float)acc[m][n][r];
+                    }
+                }
+#pragma unroll
+                for (int n = 0; n < NQ; n++) {
+                    const float yn = BITS == 8 ? ym[n].w : ym[n].y;
+                    if (mode == 0) {
+                        p[n] = fminf(p[n], (xnorm + yn) - 2.0f * est[n]);
+                    } else if (mode == 1) {
+                        p[n] = fminf(p[n], fcos - est[n]);
+                    } else {
+                        float tt = fl2 * (xnorm + yn);
+                        tt = tt + fcos;
+                        const float dist = tt - s_ * est[n];
+                        bad[n] = bad[n] || (ok && dist != dist);
+                        p[n] = fminf(p[n], ok ? dist : __builtin_inff());
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);  // one row at a time: bounds the live temporaries
+            }
+    // minimum over the 4 row groups: lanes j, j + 16, j + 32, j + 48
+    // (ds_bpermute, which the compiler's hazard and wait tracking covers)
+#pragma unroll
+    for (int n = 0; n < NQ; n++) {
+        float v = bad[n] ? -__builtin_inff() : p[n];
+        v = fminf(v, __shfl_xor(v, 32));
+        out[n] = fminf(v, __shfl_xor(v, 16));
+    }
+}
+
+// ---------------------------------------------------------------------------
 // k_rq8_keys<NC>: block minima of 256 queries (8 waves x 32, their codes in
 // VGPRs as B fragments) x one span of 32-row blocks, D = 64 NC.  A block's
 // codes (32 D bytes: 2 NC 1-KiB pieces, [16-byte chunk][row]), meta, code sums
@@ -179,7 +370,6 @@ __global__ __launch_bounds__(512, 2) void k_rq8_keys(RQ8Args a) {
     // so no NaN can arise, and 0 (n2x + n2y) + fcos == fcos for cosine / dot
     constexpr float FINE = 1e16f;
     const bool qfine = BITS == 8 ? (ym[0].w <= FINE && ym[1].w <= FINE) : (ym[0].y <= FINE && ym[1].y <= FINE);
-    const bool l2 = a.fl2 != 0.f;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the query loads retire before the DMA ring
 
     const int64_t b0 = (int64_t)span * a.blocks_per_span;
@@ -216,8 +406,6 @@ __global__ __launch_bounds__(512, 2) void k_rq8_keys(RQ8Args a) {
 
     const unsigned l16 = (unsigned)(g * 512 + j * 16);
     float* krow = a.key + (q0 + (lane & 31)) * a.ldk;
-    const float fD = (float)D;
-    const float s_ = 1.0f + a.fl2;
     // Waves 4-7 (each the SIMD partner of wave w - 4) run block t-1's
     // epilogue before block t's MFMAs instead of after them, so the two
     // waves of a SIMD alternate MFMA and VALU phases (MI355X_MICROARCH.md, two
@@ -255,160 +443,11 @@ __global__ __launch_bounds__(512, 2) void k_rq8_keys(RQ8Args a) {
         });
     };
     // a block's epilogue (its meta in slot sb, its sums in acc) -> the lane's
-    // key of it (lanes 0-31)
+    // key of it (lanes 0-15: queries j, lanes 16-31: queries 16 + j)
     auto epilogue = [&](unsigned sb) -> float {
-        // the lane's rows 16m + 4g + r: meta, code sums; the block's valid word
-        i32x4_t mt[2][4], cs[2];
-        const unsigned mb = sb + MB + (unsigned)(g * 64);
-        mt[0][0] = lds_ld16_o<0>(mb);
-        mt[0][1] = lds_ld16_o<16>(mb);
-        mt[0][2] = lds_ld16_o<32>(mb);
-        mt[0][3] = lds_ld16_o<48>(mb);
-        mt[1][0] = lds_ld16_o<256>(mb);
-        mt[1][1] = lds_ld16_o<272>(mb);
-        mt[1][2] = lds_ld16_o<288>(mb);
-        mt[1][3] = lds_ld16_o<304>(mb);
-        const unsigned cb = sb + SB + (unsigned)(g * 16);
-        cs[0] = lds_ld16_o<0>(cb);
-        cs[1] = lds_ld16_o<64>(cb);
-        uint32_t vw0 = rq8_lds_ld4(sb + VB);
-        qs_wait_lgkm<0>();
-        // the loaded registers are defined only after the wait: tie them to it,
-        // or the compiler may schedule their uses above it
-        asm volatile("" : "+v"(mt[0][0]), "+v"(mt[0][1]), "+v"(mt[0][2]), "+v"(mt[0][3]), "+v"(vw0));
-        asm volatile("" : "+v"(mt[1][0]), "+v"(mt[1][1]), "+v"(mt[1][2]), "+v"(mt[1][3]));
-        asm volatile("" : "+v"(cs[0]), "+v"(cs[1]));
-        const uint32_t vw = __builtin_amdgcn_readfirstlane(vw0);
-        if (a.dbg_serial & 8) return __int_as_float(acc[0][0][0] ^ acc[1][1][3] ^ mt[0][0][0] ^ cs[1][0]);  // timing: no epilogue math
-        float p[2] = {__builtin_inff(), __builtin_inff()};
-        bool bad[2] = {false, false};
-        // the fast forms: every row valid, every norm <= FINE (wave-uniform);
-        // l2: (1 (n2x + n2y) + 0) - 2 est, cosine / dot: (0 (..) + fcos) - 1 est
-        bool fine = qfine;
-    #pragma unroll
-        for (int m = 0; m < 2; m++)
-    #pragma unroll
-            for (int r = 0; r < 4; r++) fine = fine && __int_as_float(mt[m][r][BITS == 8 ? 3 : 1]) <= FINE;
-        const int mode = (vw == 0xFFFFFFFFu && __all(fine) && !(a.dbg_serial & 4)) ? (l2 ? 0 : 1) : 2;
-        if (mode != 2 && !(a.dbg_serial & 32)) {
-            // the fast forms on packed fp32 (v_pk_mul_f32 / v_pk_add_f32: the
-            // two query halves n = 0, 1 of a row in one instruction, each
-            // element rounded as the scalar op would).  cosine / dot: fl(fcos -
-            // est) falls as est grows, so the block's minimum is fcos - (the
-            // maximum est) and the subtraction moves out of the row loop.
-            const f32x2_t yx = {ym[0].x, ym[1].x}, yz = {ym[0].z, ym[1].z};
-            const f32x2_t yyv = {BITS == 8 ? ym[0].y : ym[0].x, BITS == 8 ? ym[1].y : ym[1].x};
-            const f32x2_t ynv = {BITS == 8 ? ym[0].w : ym[0].y, BITS == 8 ? ym[1].w : ym[1].y};
-            f32x2_t best = {mode == 0 ? __builtin_inff() : -__builtin_inff(), mode == 0 ? __builtin_inff() : -__builtin_inff()};
-    #pragma unroll
-            for (int m = 0; m < 2; m++)
-    #pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    f32x2_t est;
-                    float xnorm;
-                    if constexpr (BITS == 8) {
-                        const float xl = __int_as_float(mt[m][r][0]);
-                        const float xs = __int_as_float(mt[m][r][1]);
-                        const float xz = __int_as_float(mt[m][r][2]);
-                        xnorm = __int_as_float(mt[m][r][3]);
-                        const float a1 = fD * xl;
-                        const int kx = (int)(128u * (uint32_t)cs[m][r]) - 16384 * D;
-                        const f32x2_t dotv = {(float)(uint32_t)(acc[m][0][r] + kx), (float)(uint32_t)(acc[m][1][r] + kx)};
-                        const f32x2_t e1 = f32x2_t{a1, a1} * yx;
-                        const f32x2_t e2 = f32x2_t{xl, xl} * yz;
-                        const f32x2_t e3 = yx * f32x2_t{xz, xz};
-                        f32x2_t e4 = f32x2_t{xs, xs} * yyv;
-                        e4 = e4 * dotv;
-                        est = ((e1 + e2) + e3) + e4;
-                    } else {
-                        const float xs = __int_as_float(mt[m][r][0]);
-                        xnorm = __int_as_float(mt[m][r][1]);
-                        const f32x2_t accv = {(float)acc[m][0][r], (float)acc[m][1][r]};
-                        est = (yyv * f32x2_t{xs, xs}) * accv;
-                    }
-                    if (mode == 0) {
-                        const f32x2_t v = (f32x2_t{xnorm, xnorm} + ynv) - f32x2_t{2.0f, 2.0f} * est;
-                        best[0] = fminf(best[0], v[0]);
-                        best[1] = fminf(best[1], v[1]);
-                    } else {
-                        best[0] = fmaxf(best[0], est[0]);
-                        best[1] = fmaxf(best[1], est[1]);
-                    }
-                }
-            if (mode == 1) {
-                p[0] = a.fcos - best[0];
-                p[1] = a.fcos - best[1];
-            } else {
-                p[0] = best[0];
-                p[1] = best[1];
-            }
-        } else
-    #pragma unroll
-        for (int m = 0; m < 2; m++)
-    #pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const bool ok = (vw >> (16 * m + 4 * g + r)) & 1u;
-                float est[2], xnorm;
-                if constexpr (BITS == 8) {
-                    // est = ((D lx ly + lx cy) + ly cx) + sx sy dot (the reference's order)
-                    const float xl = __int_as_float(mt[m][r][0]);
-                    const float xs = __int_as_float(mt[m][r][1]);
-                    const float xz = __int_as_float(mt[m][r][2]);
-                    xnorm = __int_as_float(mt[m][r][3]);
-                    const float a1 = fD * xl;
-                    const int kx = (int)(128u * (uint32_t)cs[m][r]) - 16384 * D;
-    #pragma unroll
-                    for (int n = 0; n < 2; n++) {
-                        const uint32_t dot = (uint32_t)(acc[m][n][r] + kx);
-                        float e1 = a1 * ym[n].x;
-                        const float e2 = xl * ym[n].z;
-                        const float e3 = ym[n].x * xz;
-                        float e4 = xs * ym[n].y;
-                        e4 = e4 * (float)dot;
-                        float e = e1 + e2;
-                        e = e + e3;
-                        est[n] = e + e4;
-                    }
-                } else {
-                    // rq-1 (BinaryRQDistancer.Distance, binary_rotational_quantization.go:364-385):
-                    // acc = sum s_x w_q = 31 qdim - sum_p 2^(p+1) popcount(x ^ plane_p) exactly
-                    const float xs = __int_as_float(mt[m][r][0]);
-                    xnorm = __int_as_float(mt[m][r][1]);
-    #pragma unroll
-                    for (int n = 0; n < 2; n++) {
-                        const float e = ym[n].x * xs;
-                        est[n] = e * (float)acc[m][n][r];
-                    }
-                }
-    #pragma unroll
-                for (int n = 0; n < 2; n++) {
-                    const float yn = BITS == 8 ? ym[n].w : ym[n].y;
-                    if (mode == 0) {
-                        p[n] = fminf(p[n], (xnorm + yn) - 2.0f * est[n]);
-                    } else if (mode == 1) {
-                        p[n] = fminf(p[n], a.fcos - est[n]);
-                    } else {
-                        float tt = a.fl2 * (xnorm + yn);
-                        tt = tt + a.fcos;
-                        const float dist = tt - s_ * est[n];
-                        bad[n] = bad[n] || (ok && dist != dist);
-                        p[n] = fminf(p[n], ok ? dist : __builtin_inff());
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);  // one row at a time: bounds the live temporaries
-            }
-    #pragma unroll
-        for (int n = 0; n < 2; n++)
-            if (bad[n]) p[n] = -__builtin_inff();
-        // minimum over the 4 row groups: lanes j, j + 16, j + 32, j + 48
-        // (ds_bpermute, which the compiler's hazard and wait tracking covers)
-        float m0 = p[0], m1 = p[1];
-        m0 = fminf(m0, __shfl_xor(m0, 32));
-        m1 = fminf(m1, __shfl_xor(m1, 32));
-        m0 = fminf(m0, __shfl_xor(m0, 16));
-        m1 = fminf(m1, __shfl_xor(m1, 16));
-        // lanes 0-15: queries j (m0); lanes 16-31: queries 16 + j (m1)
-        return (lane & 16) ? m1 : m0;
+        float m[2];
+        rq8_block_min<BITS, 2>(acc, sb + MB, sb + SB, sb + VB, ym, qfine, D, a.fl2, a.fcos, a.dbg_serial, lane, m);
+        return (lane & 16) ? m[1] : m[0];
     };
     for (int t = 0; t <= nsteps; t++) {
         const int cur = t % NBUF;
@@ -443,6 +482,198 @@ __global__ __launch_bounds__(512, 2) void k_rq8_keys(RQ8Args a) {
         }
     }
     if (!late && nsteps > 0 && lane < 32) krow[b0 + nsteps - 1] = pend;
+}
+
+// ---------------------------------------------------------------------------
+// k_rq8_keys_cp<NP, BITS>: k_rq8_keys for 1024 < D <= 4096 (NC = a.nc = D / 64
+// in 17..64): the same keys, a 32-row block streamed in NP =
+// ceil(NC / 16) column parts.  In the rq_tile_u4 layout the 16 chunks of a
+// part are one contiguous 32-KiB run of the block (2 KiB per chunk), so a ring
+// slot is 32 KiB + the 656 bytes of meta, code sums and valid word that only
+// the block's last part brings; 4 slots, 3 parts in flight.  The last part
+// holds nl = NC - 16 (NP - 1) chunks (1..16, a run-time count: one
+// instantiation per part count and bit width, not per NC).
+//   A wave holds 16 queries (Qf: 4 registers per chunk, zero past NC) and both
+// row halves of the block: acc[m] (8 registers) carries from part to part, the
+// C input of the block's first chunk is 128 Sy.  NP = 2 (NC <= 32): 8 waves,
+// 128 queries per workgroup, 128 fragment registers of the 256 a wave has at
+// two waves per SIMD.  NP = 3, 4: 4 waves, one per SIMD with the whole unified
+// register file (512), 64 queries per workgroup.
+//   One barrier per part.  A part's chunks run in groups of GS (2 / 4); a
+// group's A fragments (2 ds_read_b128 per chunk) are read while the group
+// before it multiplies, and a group past nl is skipped by a wave-uniform
+// branch around its MFMAs only: no register written by an LDS read is defined
+// or used under a branch of its own, the reads one group past the ragged end
+// are issued and drained unused (they stay inside the slot), and a partly
+// filled group multiplies stale bytes by the zero fragments.  The last part
+// runs the shared epilogue (rq8_block_min); the block's key is stored after
+// the next barrier, in the next block's first part.  Counted waits as in
+// k_rq8_keys: a wave's vector-memory ops retire in order, so vmcnt leaves in
+// flight exactly the parts issued after the awaited one and the key stores
+// since.
+// ---------------------------------------------------------------------------
+constexpr int RQ8_CP_PART = 16 * 2048;           // code bytes of a full part
+constexpr int RQ8_CP_SLOT = RQ8_CP_PART + 656;   // + meta (512), code sums (128), valid word
+constexpr int RQ8_CP_NBUF = 4;
+__host__ __device__ constexpr int rq8_cp_parts(int NC) { return (NC + 15) / 16; }
+__host__ __device__ constexpr int rq8_cp_waves(int NP) { return NP <= 2 ? 8 : 4; }
+
+template <int NP, int BITS>
+__global__ __launch_bounds__(64 * rq8_cp_waves(NP)) void k_rq8_keys_cp(RQ8Args a) {
+    constexpr int NW = rq8_cp_waves(NP);
+    constexpr int PART = RQ8_CP_PART, MB = PART, SB = PART + 512, VB = PART + 640, SLOT = RQ8_CP_SLOT;
+    constexpr int NBUF = RQ8_CP_NBUF, AHEAD = NBUF - 1;
+    constexpr int PWF = 32 / NW;               // loads per wave of a full part (32 1-KiB pieces)
+    constexpr int PWMAX = (35 + NW - 1) / NW;  // ... of a 16-chunk last part (+ meta, sums, valid word)
+    constexpr int GS = NW == 8 ? 2 : 4;        // chunks per group
+    constexpr int NG = 16 / GS;
+    static_assert(BITS == 8 || BITS == 1, "rq-8 or rq-1");
+    static_assert(NP >= 2 && NP <= 4, "17 <= NC <= 64");
+    extern __shared__ __attribute__((aligned(16))) unsigned char rsm[];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int NC = a.nc, D = 64 * NC;
+    const int nl = NC - 16 * (NP - 1);      // chunks of the last part
+    const int npl = 2 * nl + 3;             // its pieces
+    const int pwl = (npl + NW - 1) / NW;    // its loads per wave (padded: every wave issues pwl)
+    const int64_t CB = (int64_t)32 * D;     // code bytes per block
+    const int total = a.nqg * a.nspans;
+    const int b = blockIdx.x;
+    // XCD-aware order: the query groups of one span share an XCD (its L2)
+    const int logical = (total % 8 == 0) ? (b % 8) * (total / 8) + (b / 8) : b;
+    const int span = logical / a.nqg, grp = logical % a.nqg;
+    const int j = lane & 15, g = lane >> 4;
+    const int64_t q0 = (int64_t)grp * (16 * NW) + wave * 16;
+
+    // Qf[c]: query q0 + j, columns 64c + 16g .. +15
+    i32x4_t Qf[16 * NP];
+    {
+        const unsigned char* qp = a.Qp + (q0 + j) * D + 16 * g;
+        static_for<0, 16 * NP>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            Qf[c] = *reinterpret_cast<const i32x4_t*>(qp + 64 * (c < NC ? c : NC - 1));
+            if (c >= NC) Qf[c] = i32x4_t{0, 0, 0, 0};
+        });
+    }
+    float4 ym[1];
+    ym[0] = a.qmeta[q0 + j];
+    const int ky = BITS == 8 ? (int)(128u * a.qcsum[q0 + j]) : 0;
+    const i32x4_t C0 = {ky, ky, ky, ky};
+    const bool qfine = (BITS == 8 ? ym[0].w : ym[0].y) <= 1e16f;  // (rq8_block_min's FINE)
+    const float fl2 = a.fl2, fcos = a.fcos;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the query loads retire before the DMA ring
+
+    const int64_t b0 = (int64_t)span * a.blocks_per_span;
+    int64_t b1 = b0 + a.blocks_per_span;
+    if (b1 > a.nblk) b1 = a.nblk;
+    const int nsteps = b1 > b0 ? (int)(b1 - b0) : 0;
+    const int S = nsteps * NP;  // parts to stream
+    const unsigned ring = lds_addr(rsm);
+    // part s = block s / NP, columns 1024 (s % NP) ..
+    auto issue = [&](int s) {
+        const int t = s / NP, p = s - t * NP;
+        const int64_t blk = b0 + t;
+        const bool last = p == NP - 1;
+        const int ncode = last ? 2 * nl : 32, np = last ? npl : 32, pw = last ? pwl : PWF;
+        const unsigned char* gb = a.codes + blk * CB + (int64_t)p * PART;  // the part's contiguous run (rq_tile_u4)
+        const unsigned sb = ring + (unsigned)((s % NBUF) * SLOT);
+        static_for<0, PWMAX>([&](auto jc) {
+            constexpr int jj = decltype(jc)::value;
+            if (jj < pw) {
+                int pc = wave + NW * jj;
+                if (pc >= np) pc -= np;  // padding: a copy of a piece another wave loads (same bytes, same place)
+                if (pc < ncode) {
+                    __builtin_amdgcn_global_load_lds(gb + pc * 1024 + 16 * lane,
+                                                     (lds_ptr_t)(size_t)(sb + (unsigned)(pc * 1024)), 16, 0, 0);
+                } else if (pc == ncode) {
+                    if (lane < 32)
+                        __builtin_amdgcn_global_load_lds(a.meta + blk * 32 + lane, (lds_ptr_t)(size_t)(sb + MB), 16, 0, 0);
+                } else if (pc == ncode + 1) {
+                    if (lane < 8)
+                        __builtin_amdgcn_global_load_lds(a.csum + blk * 32 + 4 * lane, (lds_ptr_t)(size_t)(sb + SB), 16, 0,
+                                                         0);
+                } else {
+                    if (lane == 0)
+                        __builtin_amdgcn_global_load_lds(a.valid + blk, (lds_ptr_t)(size_t)(sb + VB), 4, 0, 0);
+                }
+            }
+        });
+    };
+    for (int s = 0; s < AHEAD && s < S; s++) issue(s);
+
+    const unsigned l16 = (unsigned)(g * 512 + j * 16);
+    float* krow = a.key + (q0 + j) * a.ldk;
+    i32x4_t acc[2][1];
+    float pend = 0.f;  // the key of the block before, stored after the next barrier
+    // part P of a block in slot sb: n chunks (16, or nl in the last part)
+    auto mfma_part = [&](auto PP, unsigned sb) {
+        constexpr int P = decltype(PP)::value;
+        const int n = P == NP - 1 ? nl : 16;
+        const unsigned ab = sb + l16;
+        i32x4_t A[2][GS][2];
+        auto read_group = [&](auto GG) {
+            constexpr int G = decltype(GG)::value;
+            static_for<0, GS>([&](auto kk) {
+                constexpr int k = decltype(kk)::value;
+                A[G & 1][k][0] = lds_ld16_o<(G * GS + k) * 2048>(ab);
+                A[G & 1][k][1] = lds_ld16_o<(G * GS + k) * 2048 + 256>(ab);
+            });
+        };
+        read_group(std::integral_constant<int, 0>{});
+        // group G + 1 nests in group G's branch: its fragments are read where they are used
+        auto group = [&](auto self, auto GG) -> void {
+            constexpr int G = decltype(GG)::value;
+            if (G * GS < n) {
+                if constexpr (G + 1 < NG) read_group(std::integral_constant<int, G + 1>{});
+                static_for<0, GS>([&](auto kk) {
+                    constexpr int k = decltype(kk)::value;
+                    constexpr int c = G * GS + k;
+                    // in flight behind chunk c's two reads: the rest of its group and the next group
+                    qs_wait_lgkm<2 * (GS - 1 - k) + (G + 1 < NG ? 2 * GS : 0)>();
+                    asm volatile("" : "+v"(A[G & 1][k][0]), "+v"(A[G & 1][k][1]));
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int m = 0; m < 2; m++)
+                        acc[m][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[G & 1][k][m], Qf[16 * P + c],
+                                                                          (P == 0 && c == 0) ? C0 : acc[m][0], 0, 0, 0);
+                });
+                if constexpr (G + 1 < NG) self(self, std::integral_constant<int, G + 1>{});
+            }
+        };
+        group(group, std::integral_constant<int, 0>{});
+        qs_wait_lgkm<0>();  // the reads past a ragged end: drained before their registers are reused
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    for (int t = 0; t < nsteps; t++) {
+        static_for<0, NP>([&](auto PP) {
+            constexpr int P = decltype(PP)::value;
+            const int s = t * NP + P;
+            // part s landed: leave in flight the parts issued after it (s + 1 ..
+            // s + AHEAD - 1) and the key stores of the steps since its issue
+            // (steps s - AHEAD + 1 .. s - 1 that begin a block other than the first)
+            int later = 0;
+            static_for<1, AHEAD>([&](auto kk) {
+                constexpr int k = decltype(kk)::value;
+                if (s + k < S) later += ((P + k) % NP == NP - 1) ? pwl : PWF;
+                if (((P - k) % NP + NP) % NP == 0 && s - k >= NP) later += 1;
+            });
+            qs_wait_vm(later);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            if (P == 0 && t > 0 && lane < 16) krow[b0 + t - 1] = pend;
+            if (s + AHEAD < S) issue(s + AHEAD);
+            const unsigned sb = ring + (unsigned)((s % NBUF) * SLOT);
+            mfma_part(PP, sb);
+            if constexpr (P == NP - 1) {
+                float m[1];
+                rq8_block_min<BITS, 1>(acc, sb + MB, sb + SB, sb + VB, ym, qfine, D, fl2, fcos, 0, lane, m);
+                pend = m[0];
+            }
+        });
+    }
+    if (nsteps > 0 && lane < 16) krow[b0 + nsteps - 1] = pend;
 }
 
 // ---------------------------------------------------------------------------

@@ -55,6 +55,12 @@ int set_err(int code, const char* fmt, ...);
 // bq_packed.hip: 32-row BQ block minima from the packed codes (a hipError_t)
 int wv_bq_packmin(hipStream_t s, const uint64_t* codes, int64_t ccap, int words, const uint32_t* valid, int64_t nslots,
                   const uint64_t* qcodes, int64_t ldq, const int32_t* qlist, int nlist, int64_t nblk, float* bmin);
+// rq8_wide.hip: k_rq8_keys_cp (rq-8 / rq-1 block minima, 1024 < D <= 4096) for a.nc chunks; a hipError_t.
+// a.nqg counts query groups of rq8_wide_queries(a.nc)
+int wv_rq8_keys_wide(const RQ8Args& a, hipStream_t s, int bits);
+constexpr int rq8_wide_queries(int nc) { return 16 * rq8_cp_waves(rq8_cp_parts(nc)); }
+// option rq_wide = -1 takes that route for rq-1 only: rq-8 loses the whole call at B = 256
+constexpr bool rq_wide_auto(int bits) { return bits == 1; }
 // the width classes (code words) option bq_pack = -1 sends there: DESIGN §3.5d
 constexpr bool BQ_PACK_AUTO_25_32 = true, BQ_PACK_AUTO_33_64 = true;
 
@@ -293,6 +299,7 @@ struct wv_index {
     DBuf rq8Qp, rq8Qcs, rq8Qm, rq8Fq, rq8Fm;                  // rq-8 MFMA route: query planes, flagged queries
     DBuf rq8M;                                                // a multi-allow batch: the select's threshold M per query
     int rq_mfma = 1;
+    int rq_wide = -1;       // option rq_wide: 1024 < D <= 4096 on the matrix cores too (k_rq8_keys_cp): 1, never (0), auto (-1)
     // per-query allow lists (wv_index_search_by_vector_batch_multi_allow):
     // pqa_cur is the shared launch in flight, set by pqa_run for the length of
     // its search_core call only (the exact pass and the replays of search_qs

@@ -752,6 +752,10 @@ extern "C" int wv_index_set_option(wv_index* idx, const char* key, int64_t value
     else if (k == "q8_prio") idx->q8_prio = value ? 1 : 0;
     else if (k == "sel_split_max") idx->sel_split_max = value;
     else if (k == "rq_mfma") idx->rq_mfma = value ? 1 : 0;
+    else if (k == "rq_wide") {  // rq-8 / rq-1 above 1024 rotated dims on the integer MFMA: 1 always (<= 4096), 0 never, -1 auto
+        if (value < -1 || value > 1) return set_err(WV_ERR_INVALID, "rq_wide must be -1, 0 or 1");
+        idx->rq_wide = (int)value;
+    }
     else if (k == "q8_bm_min") idx->q8_bm_min = value;
     else if (k == "rq_serial") idx->rq_serial = (int)value;
     else if (k == "exact_cap") idx->exact_cap = value ? 1 : 0;
