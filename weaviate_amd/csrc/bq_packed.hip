@@ -48,6 +48,8 @@
 
 #include <algorithm>
 
+#include "dyn_lds.h"
+
 namespace wv {
 namespace {
 
@@ -236,11 +238,8 @@ int wv_bq_packmin(hipStream_t s, const uint64_t* codes, int64_t ccap, int words,
     const dim3 grid((unsigned)qg, (unsigned)((nblk + bps - 1) / bps));
 #define WV_PK(QTV)                                                                                                \
     do {                                                                                                          \
-        if (lds > 64 * 1024) {                                                                                    \
-            const hipError_t e = hipFuncSetAttribute((const void*)k_bq_packmin<QTV>,                              \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);       \
-            if (e != hipSuccess) return (int)e;                                                                   \
-        }                                                                                                         \
+        const int e = set_dyn_lds((const void*)k_bq_packmin<QTV>, lds);                                           \
+        if (e != (int)hipSuccess) return e;                                                                       \
         k_bq_packmin<QTV><<<grid, PK_THREADS, lds, s>>>(codes, ccap, words, valid, nslots, qcodes, ldq, qlist, nlist, \
                                                         nblk, bps, bmin);                                         \
     } while (0)

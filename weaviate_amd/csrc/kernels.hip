@@ -904,10 +904,8 @@ static inline hipError_t launch_replay_scan(int k, unsigned grid, hipStream_t st
     if (grid == 0) return hipSuccess;
     const size_t lds = replay_scan_lds(k);
     const void* fn = k <= PACKED_REPLAY_MAX_K ? (const void*)k_replay_scan<true> : (const void*)k_replay_scan<false>;
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = (hipError_t)set_dyn_lds(fn, lds);
+    if (e != hipSuccess) return e;
     if (k <= PACKED_REPLAY_MAX_K) k_replay_scan<true><<<grid, 64, lds, st>>>(args...);
     else k_replay_scan<false><<<grid, 64, lds, st>>>(args...);
     return hipGetLastError();

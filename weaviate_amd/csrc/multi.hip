@@ -1023,8 +1023,7 @@ int rheap_parallel(wv_multi* m, int64_t nc, int Rk, int cap, BoundsFn bounds_fn,
         const size_t lds = (size_t)R.rank * Rk * 4;
         if (lds > 160 * 1024) return set_err(WV_ERR_UNSUPPORTED, "prefix bound: %d ranks x %d minima exceed LDS", R.rank, Rk);
         HIPCHK(hipSetDevice(R.dev));
-        if (lds > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)k_prefix_bound, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(set_dyn_lds((const void*)k_prefix_bound, lds));
         k_prefix_bound<<<(unsigned)nc, 256, lds, R.s>>>(R.rank, nullptr, (int)nc, Rk, Rk, nc, R.gbnd.as<float>(), nullptr,
                                                         nullptr, nullptr, nullptr, R.fki.as<uint64_t>(), R.fkd.as<float>(),
                                                         R.fkn.as<int32_t>());
@@ -1194,13 +1193,9 @@ int multi_search_bq(wv_multi* m, int64_t nq, int64_t d, int k, uint64_t* o_i0, f
         HIPCHK(hipSetDevice(H.dev));
         rc = ensure_rank_iota(H, nc, H.s);
         if (rc) return rc;
-        const size_t lds_f = (size_t)k * (sizeof(uint64_t) + sizeof(float)) + 16;
-        if (lds_f > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)k_bq_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-        k_bq_final<<<(unsigned)nc, 64, lds_f, H.s>>>(candv(H).as<uint64_t>(), H.gEall.as<float>(),
-                                                     cnv(H).as<int32_t>(), H.iota.as<int32_t>(), (int)nc, Rk, k, W,
-                                                     m->id_stride, o_i0 + c0 * k, o_d0 + c0 * k, o_n0 + c0, 0);
-        HIPCHK(hipGetLastError());
+        rc = launch_bq_final(H.s, nc, Rk, k, W, m->id_stride, H.iota.as<int32_t>(), candv(H).as<uint64_t>(),
+                             cnv(H).as<int32_t>(), H.gEall.as<float>(), o_i0 + c0 * k, o_d0 + c0 * k, o_n0 + c0);
+        if (rc) return rc;
     }
     return WV_OK;
 }
@@ -1293,24 +1288,14 @@ int multi_search_quant(wv_multi* m, int64_t nq, int64_t d, int k, uint64_t* o_i0
         HIPCHK(hipSetDevice(H.dev));
         rc = ensure_rank_iota(H, nc, H.s);
         if (rc) return rc;
-        if (form == 1) {  // searchByVectorQuantized's rescoring heap, candidates ascending
-            const size_t lds_f = (size_t)k * (sizeof(uint64_t) + sizeof(float)) + 16;
-            if (lds_f > 64 * 1024)
-                HIPCHK(hipFuncSetAttribute((const void*)k_bq_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-            k_bq_final<<<(unsigned)nc, 64, lds_f, H.s>>>(H.cand.as<uint64_t>(), H.gEall.as<float>(), H.un.as<int32_t>(),
-                                                         H.iota.as<int32_t>(), (int)nc, Rk, k, W, m->id_stride,
-                                                         o_i0 + c0 * k, o_d0 + c0 * k, o_n0 + c0, 1);
-        } else {  // h.rescore
-            const size_t lds_q = (size_t)(k + 1) * (sizeof(uint64_t) + sizeof(float)) + 16;
-            if (lds_q > 64 * 1024)
-                HIPCHK(hipFuncSetAttribute((const void*)k_pq_rescore_final, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_q));
-            k_pq_rescore_final<<<(unsigned)nc, 64, lds_q, H.s>>>(nullptr, H.gEall.as<float>(), H.un.as<int32_t>(),
-                                                                 H.iota.as<int32_t>(), (int)nc, Rk, k, 0, o_i0 + c0 * k,
-                                                                 o_d0 + c0 * k, o_n0 + c0, H.cand.as<uint64_t>(), W,
-                                                                 m->id_stride);
-        }
-        HIPCHK(hipGetLastError());
+        if (form == 1)  // searchByVectorQuantized's rescoring heap, candidates ascending
+            rc = launch_bq_final(H.s, nc, Rk, k, W, m->id_stride, H.iota.as<int32_t>(), H.cand.as<uint64_t>(),
+                                 H.un.as<int32_t>(), H.gEall.as<float>(), o_i0 + c0 * k, o_d0 + c0 * k, o_n0 + c0, 1);
+        else  // h.rescore
+            rc = launch_pq_rescore_final(H.s, nullptr, H.gEall.as<float>(), H.un.as<int32_t>(), H.iota.as<int32_t>(), nc,
+                                         Rk, k, 0, o_i0 + c0 * k, o_d0 + c0 * k, o_n0 + c0, H.cand.as<uint64_t>(), W,
+                                         m->id_stride);
+        if (rc) return rc;
     }
     return WV_OK;
 }

@@ -72,7 +72,7 @@ int launch_blk_replay(wv_index* idx, hipStream_t s, const float* key, int64_t ld
         const int64_t g3 = std::min<int64_t>(max_list, 2048);
 #define WV_RPH(M, V)                                                                                            \
     do {                                                                                                        \
-        if (hlds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_rp_heap<M, V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hlds)); \
+        HIPCHK(set_dyn_lds((const void*)k_rp_heap<M, V>, hlds));                                                \
         k_rp_heap<M, V><<<(unsigned)g3, 64, hlds, s>>>(key, ldk, nb, eps, qinfo, idx->X, idx->dpad, valid, idx->hiwater, Qn, idx->dims, list, counters, nlist, k, kout, idx->id_base, oi, od, on, in_i, in_d, in_n, extract, by_list, idx->rpBlk.as<uint32_t>(), idx->rpLb.as<float>(), idx->rpE.as<float>(), idx->rpVm.as<uint32_t>(), idx->rpOff.as<int32_t>(), idx->rpTot.as<int32_t>(), rec_i, rec_d, rec_n, rec_cap, idx->cur_vq); \
     } while (0)
         switch (metric) {
@@ -106,7 +106,8 @@ int launch_blk_replay(wv_index* idx, hipStream_t s, const float* key, int64_t ld
     if (rlds > 160 * 1024) return set_err(WV_ERR_UNSUPPORTED, "k %d too large for the replay heap", k);
 #define WV_RP(M, V)                                                                                             \
     do {                                                                                                        \
-        if (rlds > 64 * 1024) { HIPCHK(hipFuncSetAttribute((const void*)k_blk_replay<M, V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds)); HIPCHK(hipFuncSetAttribute((const void*)k_blk_replay<M, V, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds)); } \
+        HIPCHK(set_dyn_lds((const void*)k_blk_replay<M, V>, rlds));                                             \
+        HIPCHK(set_dyn_lds((const void*)k_blk_replay<M, V, 1>, rlds));                                          \
         if (idx->replay_dbg) k_blk_replay<M, V, 1><<<(unsigned)max_list, 64, rlds, s>>>(key, ldk, nb, eps, qinfo, idx->X, idx->dpad, valid, idx->hiwater, Qn, idx->dims, list, counters, nlist, k, kout, idx->id_base, oi, od, on, in_i, in_d, in_n, extract, by_list, Xb, idx->dpb, idx->xnorm2, idx->qsmax, idx->d_maxn2, gd, gacc_r, idx->cur_vq); \
         else k_blk_replay<M, V><<<(unsigned)max_list, 64, rlds, s>>>(key, ldk, nb, eps, qinfo, idx->X, idx->dpad, valid, idx->hiwater, Qn, idx->dims, list, counters, nlist, k, kout, idx->id_base, oi, od, on, in_i, in_d, in_n, extract, by_list, Xb, idx->dpb, idx->xnorm2, idx->qsmax, idx->d_maxn2, gd, gacc_r, idx->cur_vq); \
     } while (0)

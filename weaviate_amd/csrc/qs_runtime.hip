@@ -43,7 +43,7 @@ int invert_lists(wv_index* idx, hipStream_t s, const uint32_t* cand, const int32
 // "set the dynamic-LDS limit, launch" of the block-key kernels
 template <typename A>
 static hipError_t launch_dyn_lds(void (*kern)(A), dim3 grid, unsigned threads, size_t lds, hipStream_t s, const A& a) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = (hipError_t)set_dyn_lds((const void*)kern, lds);
     if (e != hipSuccess) return e;
     kern<<<grid, threads, lds, s>>>(a);
     return hipSuccess;
@@ -789,8 +789,7 @@ extern "C" int wv_heap_merge_records(int32_t device, int32_t nlist, int32_t k, i
     HIPCHK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = (size_t)k * (sizeof(uint64_t) + sizeof(float)) + 16;
-    if (lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)k_heap_merge_records, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(set_dyn_lds((const void*)k_heap_merge_records, lds));
     k_heap_merge_records<<<(unsigned)nlist, 64, lds, s>>>(nlist, k, world, cap, d_st_ids, d_st_dists, d_st_n, d_rec_ids,
                                                           d_rec_dists, d_rec_n, d_out_ids, d_out_dists, d_out_n,
                                                           d_unresolved);

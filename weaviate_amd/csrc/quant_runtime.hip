@@ -60,13 +60,8 @@ static int bq_begin(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t n
     idx->stats.batches++;
     idx->stats.replayed_queries += (uint64_t)nq;
     const int64_t nblk = bq_nblk(idx);
-    // identity query list
-    HIPCHK(idx->ident.ensure((size_t)nq * sizeof(int32_t)));
-    {
-        std::vector<int32_t> id((size_t)nq);
-        for (int64_t i = 0; i < nq; i++) id[i] = (int32_t)i;
-        HIPCHK(hipMemcpyAsync(idx->ident.p, id.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    }
+    rc = ensure_ident(idx, nq, s);
+    if (rc) return rc;
     constexpr int QPB = 16;
     // one group of block minima up to 4 GiB (the 32-row minima of the integer
     // route are 8x the 256-row ones: C4's 2048 x 195k blocks = 1.6 GB)
@@ -208,9 +203,7 @@ static int bq_replay(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_
     if (lds_r > 160 * 1024) return set_err(WV_ERR_UNSUPPORTED, "rescore limit %d too large for the replay heap", R);
 #define WV_RPB(NWV, RECV, BLKV, PQV)                                                                            \
     do {                                                                                                        \
-        if (lds_r > 64 * 1024)                                                                                  \
-            HIPCHK(hipFuncSetAttribute((const void*)k_bq_replay<NWV, RECV, BLKV, PQV>,                          \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));                \
+        HIPCHK(set_dyn_lds((const void*)k_bq_replay<NWV, RECV, BLKV, PQV>, lds_r));                             \
         k_bq_replay<NWV, RECV, BLKV, PQV><<<(unsigned)F, 64, lds_r, s>>>(                                       \
             idx->codes, idx->cap, words, valid, nslots, qc, nq, qlist + g0, F, bm, nblk, R, idx->id_base, in_ids, \
             in_d, in_len, pop, out_ids, out_d, out_n, rec_ids, rec_d, rec_n, cap, skip, vq);                    \
@@ -291,35 +284,71 @@ static bool bq_fast(wv_index* idx, hipStream_t s, const uint32_t* valid, int64_t
     return *rc == WV_OK;
 }
 
-// Phase 3: exact distances of the candidate ids this shard holds
-static int bq_rescore(wv_index* idx, hipStream_t s, const uint64_t* ids, const int32_t* cnt, float* E) {
-    const int64_t nq = idx->bq_nq;
-    const int R = idx->bq_R;
+// ---- the final-stage launchers (rt_index.h) ----
+// Phase 3: exact distances of the candidate ids this shard holds (the identity query list in idx->ident)
+int launch_rescore_ids(wv_index* idx, hipStream_t s, const uint64_t* ids, const int32_t* cnt, int64_t nq, int R,
+                       float* E) {
     const int64_t npairs = nq * R;
-    const float* Qn = idx->qn.as<float>();
-    const int32_t* qlist = idx->ident.as<int32_t>();
-    const bool v5 = idx->variant == WV_VARIANT_AVX512;
-#define WV_RS(M, V) k_rescore_ids<M, V><<<(unsigned)((npairs + 63) / 64), 64, 0, s>>>(idx->X, idx->dpad, Qn, idx->dims, ids, cnt, qlist, (int)nq, R, idx->id_base, idx->hiwater, E)
-    switch (idx->metric) {
-    case WV_METRIC_L2_SQUARED: if (v5) WV_RS(L2, AVX512); else WV_RS(L2, AVX256); break;
-    case WV_METRIC_DOT: if (v5) WV_RS(DOT, AVX512); else WV_RS(DOT, AVX256); break;
-    case WV_METRIC_COSINE_DOT: if (v5) WV_RS(COSINE, AVX512); else WV_RS(COSINE, AVX256); break;
-    case WV_METRIC_MANHATTAN: WV_RS(MANHATTAN, AVX256); break;
-    default: WV_RS(HAMMING, AVX256); break;
-    }
-#undef WV_RS
+    for_metric_variant(idx->metric, idx->variant, [&](auto M, auto V) {
+        k_rescore_ids<M(), V()><<<(unsigned)((npairs + 63) / 64), 64, 0, s>>>(
+            idx->X, idx->dpad, idx->qn.as<float>(), idx->dims, ids, cnt, idx->ident.as<int32_t>(), (int)nq, R,
+            idx->id_base, idx->hiwater, E);
+    });
+    HIPCHK(hipGetLastError());
+    return WV_OK;
+}
+
+int launch_rescore_slots(wv_index* idx, hipStream_t s, const uint32_t* slots, int64_t nq, int R, float* E) {
+    const int64_t npairs = nq * R;
+    for_metric_variant(idx->metric, idx->variant, [&](auto M, auto V) {
+        k_rescore<M(), V()><<<(unsigned)((npairs + 63) / 64), 64, 0, s>>>(idx->X, idx->dpad, idx->qn.as<float>(),
+                                                                         idx->dims, slots, (int)nq, R, E);
+    });
+    HIPCHK(hipGetLastError());
+    return WV_OK;
+}
+
+// bilinear only: the lists come from rq8_candidates, and rq-8 / rq-1 have no hamming or manhattan distance
+int launch_rescore_list(wv_index* idx, hipStream_t s, const int32_t* list, int nlist, int R) {
+    const int64_t np = (int64_t)nlist * R;
+    for_bilinear_variant(idx->metric, idx->variant, [&](auto M, auto V) {
+        k_rescore_list<M(), V()><<<(unsigned)((np + 63) / 64), 64, 0, s>>>(
+            idx->X, idx->dpad, idx->qn.as<float>(), idx->dims, idx->ascI.as<uint64_t>(), idx->ascN.as<int32_t>(), list,
+            nlist, R, idx->id_base, idx->hiwater, idx->candE.as<float>());
+    });
     HIPCHK(hipGetLastError());
     return WV_OK;
 }
 
 // Phase 4: insertToHeap(heap, k, ...) in pop order + extractHeap
-static int bq_final(hipStream_t s, int64_t nq, int R, int k, int world, uint64_t id_stride, const int32_t* qlist,
-                    const uint64_t* ids, const int32_t* cnt, const float* E, uint64_t* o_ids, float* o_d,
-                    int32_t* o_n, int asc = 0) {
-    const size_t lds_f = (size_t)k * (sizeof(uint64_t) + sizeof(float)) + 16;
-    if (lds_f > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)k_bq_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-    k_bq_final<<<(unsigned)nq, 64, lds_f, s>>>(ids, E, cnt, qlist, (int)nq, R, k, world, id_stride, o_ids, o_d, o_n, asc);
+int launch_bq_final(hipStream_t s, int64_t nq, int R, int k, int world, uint64_t id_stride, const int32_t* qlist,
+                    const uint64_t* ids, const int32_t* cnt, const float* E, uint64_t* o_ids, float* o_d, int32_t* o_n,
+                    int asc) {
+    const size_t lds = (size_t)k * (sizeof(uint64_t) + sizeof(float)) + 16;
+    HIPCHK(set_dyn_lds((const void*)k_bq_final, lds));
+    k_bq_final<<<(unsigned)nq, 64, lds, s>>>(ids, E, cnt, qlist, (int)nq, R, k, world, id_stride, o_ids, o_d, o_n, asc);
+    HIPCHK(hipGetLastError());
+    return WV_OK;
+}
+
+int launch_pq_finish(hipStream_t s, const uint64_t* asc_ids, const float* asc_d, const int32_t* asc_n,
+                     const int32_t* qlist, int64_t nq, int R, int k, int rescore, uint64_t id_base, uint64_t* o_ids,
+                     float* o_d, int32_t* o_n, uint32_t* cand_slot, int32_t* cand_n, int trim, uint64_t* cand_ids) {
+    const size_t lds = (size_t)R * (sizeof(uint64_t) + sizeof(float)) + 16;
+    HIPCHK(set_dyn_lds((const void*)k_pq_finish, lds));
+    k_pq_finish<<<(unsigned)nq, 64, lds, s>>>(asc_ids, asc_d, asc_n, qlist, (int)nq, R, k, rescore, id_base, o_ids, o_d,
+                                              o_n, cand_slot, cand_n, trim, cand_ids);
+    HIPCHK(hipGetLastError());
+    return WV_OK;
+}
+
+int launch_pq_rescore_final(hipStream_t s, const uint32_t* cand_slot, const float* E, const int32_t* cand_n,
+                            const int32_t* qlist, int64_t nq, int R, int k, uint64_t id_base, uint64_t* o_ids,
+                            float* o_d, int32_t* o_n, const uint64_t* cand_ids, int world, uint64_t id_stride) {
+    const size_t lds = (size_t)(k + 1) * (sizeof(uint64_t) + sizeof(float)) + 16;
+    HIPCHK(set_dyn_lds((const void*)k_pq_rescore_final, lds));
+    k_pq_rescore_final<<<(unsigned)nq, 64, lds, s>>>(cand_slot, E, cand_n, qlist, (int)nq, R, k, id_base, o_ids, o_d, o_n,
+                                                     cand_ids, world, id_stride);
     HIPCHK(hipGetLastError());
     return WV_OK;
 }
@@ -357,18 +386,12 @@ int search_bq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
                        nullptr, nullptr, nullptr, 0, fast ? skip : nullptr, own_vq);
         if (rc) return rc;
     }
-    rc = bq_rescore(idx, s, idx->ascI.as<uint64_t>(), idx->cn.as<int32_t>(), idx->candE.as<float>());
+    rc = launch_rescore_ids(idx, s, idx->ascI.as<uint64_t>(), idx->cn.as<int32_t>(), nq, R, idx->candE.as<float>());
     if (rc) return rc;
-    rc = bq_final(s, nq, R, k, 1, 0, idx->ident.as<int32_t>(), idx->ascI.as<uint64_t>(), idx->cn.as<int32_t>(),
-                  idx->candE.as<float>(), o_ids, o_d, o_n);
+    rc = launch_bq_final(s, nq, R, k, 1, 0, idx->ident.as<int32_t>(), idx->ascI.as<uint64_t>(), idx->cn.as<int32_t>(),
+                         idx->candE.as<float>(), o_ids, o_d, o_n);
     if (rc) return rc;
-    if (idx->timing) {
-        HIPCHK(hipStreamSynchronize(s));
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, idx->ev0, idx->ev1);
-        idx->stats.last_select_ms = ms;
-    }
-    return WV_OK;
+    return read_select_ms(idx, s);
 }
 
 extern "C" int wv_index_debug_bqmin(wv_index* idx, int64_t q, float* mins, int64_t* nblk, int64_t* blk_rows) {
@@ -386,63 +409,64 @@ extern "C" int wv_index_debug_bqmin(wv_index* idx, int64_t q, float* mins, int64
     return WV_OK;
 }
 
+// A staged entry point of the sharded protocols (wv_index_bq_* / wv_index_quant_*):
+// nil check (args_ok: the call's other required pointers; nil: its message), idx's
+// lock and device, the batch `begun` names in flight (bq_nq / qt_nq; nullptr for the
+// *_begin calls), body(s), then the wait that a call on the null stream ends with.
+template <class F>
+static int staged_call(wv_index* idx, bool args_ok, const char* nil, const char* name, const int64_t wv_index::*begun,
+                       void* stream, F&& body) {
+    if (!idx || !args_ok) return set_err(WV_ERR_INVALID, "%s", nil);
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHK(hipSetDevice(idx->device));
+    if (begun && idx->*begun <= 0) return set_err(WV_ERR_INVALID, "%s: no batch begun", name);
+    hipStream_t s = (hipStream_t)stream;  // NULL: the null stream (ordered with the caller's default-stream work)
+    int rc = body(s);
+    if (rc) return rc;
+    if (!stream) HIPCHK(hipStreamSynchronize(s));
+    return WV_OK;
+}
+
 // ---- sharded BQ (weaviate_amd/sharded.py ShardedBQSearch) ----
 extern "C" int wv_index_bq_begin(wv_index* idx, const float* d_queries, int64_t nq, int64_t d, int32_t k,
                                  void* stream) {
-    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (idx->compression != WV_COMPRESSION_BQ) return set_err(WV_ERR_INVALID, "bq_begin: index is not BQ-compressed");
-    hipStream_t s = (hipStream_t)stream;  // NULL: the null stream (ordered with the caller's default-stream work)
-    int R = 0;
-    int64_t G = 0;
-    int rc = bq_begin(idx, s, d_queries, nq, d, k, &R, &G);
-    if (rc) return rc;
-    if (G < nq) return set_err(WV_ERR_UNSUPPORTED, "bq_begin: batch of %lld queries exceeds one block-minima group",
-                               (long long)nq);
-    rc = bq_blockmin(idx, s, idx->present, 0, (int)nq);
-    if (rc) return rc;
-    if (!stream || idx->timing) HIPCHK(hipStreamSynchronize(s));
-    if (idx->timing) {
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, idx->ev0, idx->ev1);
-        idx->stats.last_select_ms = ms;
-    }
-    return WV_OK;
+    return staged_call(idx, true, "nil index", "bq_begin", nullptr, stream, [&](hipStream_t s) -> int {
+        if (idx->compression != WV_COMPRESSION_BQ)
+            return set_err(WV_ERR_INVALID, "bq_begin: index is not BQ-compressed");
+        int R = 0;
+        int64_t G = 0;
+        int rc = bq_begin(idx, s, d_queries, nq, d, k, &R, &G);
+        if (rc) return rc;
+        if (G < nq)
+            return set_err(WV_ERR_UNSUPPORTED, "bq_begin: batch of %lld queries exceeds one block-minima group",
+                           (long long)nq);
+        rc = bq_blockmin(idx, s, idx->present, 0, (int)nq);
+        if (rc) return rc;
+        return read_select_ms(idx, s);
+    });
 }
 
 extern "C" int wv_index_bq_replay(wv_index* idx, const uint64_t* d_in_ids, const float* d_in_d,
                                   const int32_t* d_in_len, int32_t pop, uint64_t* d_out_ids, float* d_out_d,
                                   int32_t* d_out_len, void* stream) {
-    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (idx->bq_nq <= 0) return set_err(WV_ERR_INVALID, "bq_replay: no batch begun");
-    hipStream_t s = (hipStream_t)stream;  // NULL: the null stream (ordered with the caller's default-stream work)
-    int rc = bq_replay(idx, s, idx->present, 0, (int)idx->bq_nq, d_in_ids, d_in_d, d_in_len, pop, d_out_ids, d_out_d,
-                       d_out_len);
-    if (rc) return rc;
-    if (!stream) HIPCHK(hipStreamSynchronize(s));
-    return WV_OK;
+    return staged_call(idx, true, "nil index", "bq_replay", &wv_index::bq_nq, stream, [&](hipStream_t s) {
+        return bq_replay(idx, s, idx->present, 0, (int)idx->bq_nq, d_in_ids, d_in_d, d_in_len, pop, d_out_ids, d_out_d,
+                         d_out_len);
+    });
 }
 
 // parallel cross-shard BQ replay: per query the R smallest block minima of this
 // shard ([nq][R] ascending, +inf padded) -- upper bounds of distinct rows
 extern "C" int wv_index_bq_bounds(wv_index* idx, float* d_out, void* stream) {
-    if (!idx || !d_out) return set_err(WV_ERR_INVALID, "nil argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (idx->bq_nq <= 0) return set_err(WV_ERR_INVALID, "bq_bounds: no batch begun");
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nblk = bq_nblk(idx);
-    const int nbins = idx->words * 64 + 1;
-    const size_t lds = (size_t)nbins * sizeof(uint32_t);
-    if (lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)k_bq_bounds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_bq_bounds<<<(unsigned)idx->bq_nq, 256, lds, s>>>(idx->bqmin.as<float>(), nblk, nbins, idx->bq_R, d_out);
-    HIPCHK(hipGetLastError());
-    if (!stream) HIPCHK(hipStreamSynchronize(s));
-    return WV_OK;
+    return staged_call(idx, d_out != nullptr, "nil argument", "bq_bounds", &wv_index::bq_nq, stream, [&](hipStream_t s) -> int {
+        const int64_t nblk = bq_nblk(idx);
+        const int nbins = idx->words * 64 + 1;
+        const size_t lds = (size_t)nbins * sizeof(uint32_t);
+        HIPCHK(set_dyn_lds((const void*)k_bq_bounds, lds));
+        k_bq_bounds<<<(unsigned)idx->bq_nq, 256, lds, s>>>(idx->bqmin.as<float>(), nblk, nbins, idx->bq_R, d_out);
+        HIPCHK(hipGetLastError());
+        return WV_OK;
+    });
 }
 
 // parallel cross-shard BQ replay: this shard's R-heap replay from heap states
@@ -451,30 +475,18 @@ extern "C" int wv_index_bq_bounds(wv_index* idx, float* d_out, void* stream) {
 extern "C" int wv_index_bq_replay_record(wv_index* idx, const uint64_t* d_in_ids, const float* d_in_d,
                                          const int32_t* d_in_len, int32_t cap, uint64_t* d_rec_ids, float* d_rec_d,
                                          int32_t* d_rec_n, void* stream) {
-    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
-    if (cap < 1 || !d_rec_ids || !d_rec_d || !d_rec_n) return set_err(WV_ERR_INVALID, "invalid record buffers");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (idx->bq_nq <= 0) return set_err(WV_ERR_INVALID, "bq_replay_record: no batch begun");
-    hipStream_t s = (hipStream_t)stream;
-    int rc = bq_replay(idx, s, idx->present, 0, (int)idx->bq_nq, d_in_ids, d_in_d, d_in_len, 0, nullptr, nullptr,
-                       nullptr, d_rec_ids, d_rec_d, d_rec_n, cap);
-    if (rc) return rc;
-    if (!stream) HIPCHK(hipStreamSynchronize(s));
-    return WV_OK;
+    if (idx && (cap < 1 || !d_rec_ids || !d_rec_d || !d_rec_n)) return set_err(WV_ERR_INVALID, "invalid record buffers");
+    return staged_call(idx, true, "nil index", "bq_replay_record", &wv_index::bq_nq, stream, [&](hipStream_t s) {
+        return bq_replay(idx, s, idx->present, 0, (int)idx->bq_nq, d_in_ids, d_in_d, d_in_len, 0, nullptr, nullptr,
+                         nullptr, d_rec_ids, d_rec_d, d_rec_n, cap);
+    });
 }
 
 extern "C" int wv_index_bq_rescore(wv_index* idx, const uint64_t* d_ids, const int32_t* d_len, float* d_E,
                                    void* stream) {
-    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (idx->bq_nq <= 0) return set_err(WV_ERR_INVALID, "bq_rescore: no batch begun");
-    hipStream_t s = (hipStream_t)stream;  // NULL: the null stream (ordered with the caller's default-stream work)
-    int rc = bq_rescore(idx, s, d_ids, d_len, d_E);
-    if (rc) return rc;
-    if (!stream) HIPCHK(hipStreamSynchronize(s));
-    return WV_OK;
+    return staged_call(idx, true, "nil index", "bq_rescore", &wv_index::bq_nq, stream, [&](hipStream_t s) {
+        return launch_rescore_ids(idx, s, d_ids, d_len, idx->bq_nq, idx->bq_R, d_E);
+    });
 }
 
 extern "C" int wv_bq_final(int32_t device, int64_t nq, int32_t R, int32_t k, int32_t world, uint64_t id_stride,
@@ -484,14 +496,12 @@ extern "C" int wv_bq_final(int32_t device, int64_t nq, int32_t R, int32_t k, int
     if (nq <= 0) return WV_OK;
     if (k <= 0 || R < k || world < 1) return set_err(WV_ERR_INVALID, "bq_final: invalid k / R / world");
     hipStream_t s = (hipStream_t)stream;
-    std::vector<int32_t> id((size_t)nq);
-    for (int64_t i = 0; i < nq; i++) id[i] = (int32_t)i;
     DBuf ql;
     HIPCHK(ql.ensure((size_t)nq * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(ql.p, id.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    int rc = bq_final(s, nq, R, k, world, id_stride, ql.as<int32_t>(), d_ids, d_len, d_E, d_out_ids, d_out_d, d_out_n);
+    int rc = upload_iota(ql.as<int32_t>(), nq, s);
+    if (rc) return rc;
+    rc = launch_bq_final(s, nq, R, k, world, id_stride, ql.as<int32_t>(), d_ids, d_len, d_E, d_out_ids, d_out_d, d_out_n);
     HIPCHK(hipStreamSynchronize(s));  // ql is freed on return
-    ql.release();
     return rc;
 }
 
@@ -642,16 +652,12 @@ int pq_fit_rows(wv_index* idx, const float* dT, int64_t n, uint64_t seed) {
     std::vector<int32_t> active((size_t)m, iteration_threshold > 1 ? 1 : 0);
     HIPCHK(hipMemcpyAsync(act.p, active.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s));
     const dim3 rgrid((unsigned)((n + 255) / 256), (unsigned)m);
-    if (lds_c > 64 * 1024) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_km_assign_brute, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-        HIPCHK(hipFuncSetAttribute((const void*)k_km_assign_prune, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-        for (const void* f : {(const void*)k_pq_encode<0>, (const void*)k_pq_encode<1>, (const void*)k_pq_encode<2>,
-                              (const void*)k_pq_encode<4>, (const void*)k_pq_encode<8>, (const void*)k_pq_encode<16>})
-            HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-    }
+    for (const void* f : {(const void*)k_km_assign_brute, (const void*)k_km_assign_prune, (const void*)k_pq_encode<0>,
+                          (const void*)k_pq_encode<1>, (const void*)k_pq_encode<2>, (const void*)k_pq_encode<4>,
+                          (const void*)k_pq_encode<8>, (const void*)k_pq_encode<16>})
+        HIPCHK(set_dyn_lds(f, lds_c));
     const size_t lds_u = (size_t)K * ds * sizeof(double) + KM_T * sizeof(uint32_t) + (size_t)KM_T * ds * sizeof(float);
-    if (lds_u > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)k_km_update_centers, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_u));
+    HIPCHK(set_dyn_lds((const void*)k_km_update_centers, lds_u));
     k_km_assign_brute<<<rgrid, 256, lds_c, s>>>(dT, ldt, n, K, ds, C, idx->variant, nullptr, asg.as<uint32_t>());
     k_km_update_centers<<<m, KM_T, lds_u, s>>>(dT, ldt, n, K, ds, asg.as<uint32_t>(), nullptr, C);
     HIPCHK(hipGetLastError());
@@ -886,8 +892,7 @@ static int hnsw_dist(wv_index* idx, hipStream_t s, int comp, const uint32_t* val
             dim3 grid2((unsigned)((F + 1) / 2), grid.y);
 #define WV_ADC2(KCV, RPTV)                                                                                   \
     do {                                                                                                     \
-        HIPCHK(hipFuncSetAttribute((const void*)k_pq_adc2<KCV, RPTV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   (int)(2 * lds_adc)));                                                     \
+        HIPCHK(set_dyn_lds((const void*)k_pq_adc2<KCV, RPTV>, 2 * lds_adc));                                 \
         k_pq_adc2<KCV, RPTV><<<grid2, 256, 2 * lds_adc, s>>>(idx->pq_codes, pq_g16(m), m, K, valid, nslots,    \
                                                              idx->lut.as<float>(), qlist + g0, F, wrapm, ld, E, Bm); \
     } while (0)
@@ -969,14 +974,8 @@ static int hnsw_prep(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t 
                                                                        idx->qcodes.as<uint64_t>(), nq);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(idx->ident.ensure((size_t)nq * sizeof(int32_t)));
-    {
-        std::vector<int32_t> id((size_t)nq);
-        for (int64_t i = 0; i < nq; i++) id[i] = (int32_t)i;
-        HIPCHK(hipMemcpyAsync(idx->ident.p, id.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    }
     (void)R;
-    return WV_OK;
+    return ensure_ident(idx, nq, s);
 }
 
 // ---- PQ block keys on the integer matrix cores (pq_kernels.hip §3.6b) ----
@@ -1189,39 +1188,17 @@ static int pq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const
 static int hnsw_finish(wv_index* idx, hipStream_t s, int64_t nq, int R, int k, int trim, int rescore, uint64_t* o_ids,
                        float* o_d, int32_t* o_n) {
     const int32_t* qlist = idx->ident.as<int32_t>();
-    const float* Qn = idx->qn.as<float>();
     HIPCHK(idx->cslot.ensure((size_t)nq * R * sizeof(uint32_t)));
     HIPCHK(idx->cn.ensure((size_t)nq * sizeof(int32_t)));
-    const size_t lds_f = (size_t)R * (sizeof(uint64_t) + sizeof(float)) + 16;
-    if (lds_f > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)k_pq_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-    k_pq_finish<<<(unsigned)nq, 64, lds_f, s>>>(idx->ascI.as<uint64_t>(), idx->ascD.as<float>(), idx->ascN.as<int32_t>(),
-                                                qlist, (int)nq, R, k, rescore, idx->id_base, o_ids, o_d, o_n,
-                                                idx->cslot.as<uint32_t>(), idx->cn.as<int32_t>(), rescore ? trim : 0);
-    HIPCHK(hipGetLastError());
-    if (rescore) {
-        HIPCHK(idx->candE.ensure((size_t)nq * R * sizeof(float)));
-        const int64_t npairs = nq * R;
-        const bool v5 = idx->variant == WV_VARIANT_AVX512;
-#define WV_RS(M, V) k_rescore<M, V><<<(unsigned)((npairs + 63) / 64), 64, 0, s>>>(idx->X, idx->dpad, Qn, idx->dims, idx->cslot.as<uint32_t>(), (int)nq, R, idx->candE.as<float>())
-        switch (idx->metric) {
-        case WV_METRIC_L2_SQUARED: if (v5) WV_RS(L2, AVX512); else WV_RS(L2, AVX256); break;
-        case WV_METRIC_DOT: if (v5) WV_RS(DOT, AVX512); else WV_RS(DOT, AVX256); break;
-        case WV_METRIC_COSINE_DOT: if (v5) WV_RS(COSINE, AVX512); else WV_RS(COSINE, AVX256); break;
-        case WV_METRIC_MANHATTAN: WV_RS(MANHATTAN, AVX256); break;
-        default: WV_RS(HAMMING, AVX256); break;
-        }
-#undef WV_RS
-        HIPCHK(hipGetLastError());
-        const size_t lds_q = (size_t)(k + 1) * (sizeof(uint64_t) + sizeof(float)) + 16;
-        if (lds_q > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)k_pq_rescore_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-        k_pq_rescore_final<<<(unsigned)nq, 64, lds_q, s>>>(idx->cslot.as<uint32_t>(), idx->candE.as<float>(),
-                                                           idx->cn.as<int32_t>(), qlist, (int)nq, R, k, idx->id_base,
-                                                           o_ids, o_d, o_n);
-        HIPCHK(hipGetLastError());
-    }
-    return WV_OK;
+    int rc = launch_pq_finish(s, idx->ascI.as<uint64_t>(), idx->ascD.as<float>(), idx->ascN.as<int32_t>(), qlist, nq, R, k,
+                              rescore, idx->id_base, o_ids, o_d, o_n, idx->cslot.as<uint32_t>(), idx->cn.as<int32_t>(),
+                              rescore ? trim : 0);
+    if (rc || !rescore) return rc;
+    HIPCHK(idx->candE.ensure((size_t)nq * R * sizeof(float)));
+    rc = launch_rescore_slots(idx, s, idx->cslot.as<uint32_t>(), nq, R, idx->candE.as<float>());
+    if (rc) return rc;
+    return launch_pq_rescore_final(s, idx->cslot.as<uint32_t>(), idx->candE.as<float>(), idx->cn.as<int32_t>(), qlist, nq,
+                                   R, k, idx->id_base, o_ids, o_d, o_n);
 }
 
 static int search_hnsw(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k, int limit,
@@ -1292,8 +1269,7 @@ static int search_hnsw(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
         } else {
 #define WV_ADC2M(KCV)                                                                                        \
     do {                                                                                                     \
-        HIPCHK(hipFuncSetAttribute((const void*)k_pq_adc2<KCV, PQ_RPT>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   (int)(2 * lds_adc)));                                                     \
+        HIPCHK(set_dyn_lds((const void*)k_pq_adc2<KCV, PQ_RPT>, 2 * lds_adc));                               \
         k_pq_adc2<KCV, PQ_RPT><<<grid2, 256, 2 * lds_adc, s>>>(idx->pq_codes, pq_g16(m), m, K, valid, nslots,  \
                                                                idx->lut.as<float>(), qlist, (int)nq, wrapm, ld, \
                                                                nullptr, idx->rB.as<float>());                \
@@ -1383,13 +1359,7 @@ static int search_hnsw(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
     for (int b = 0; b < 2 && b < gi; b++) HIPCHK(hipStreamWaitEvent(s, idx->evr[b], 0));
     rc = hnsw_finish(idx, s, nq, R, k, trim, rescore, o_ids, o_d, o_n);
     if (rc) return rc;
-    if (idx->timing) {
-        HIPCHK(hipStreamSynchronize(s));
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, idx->ev0, idx->ev1);
-        idx->stats.last_select_ms = ms;
-    }
-    return WV_OK;
+    return read_select_ms(idx, s);
 }
 
 // the PQ index behind SearchByVector: hnsw.flatSearch with limit =
@@ -1534,9 +1504,7 @@ int search_hnsw_lists(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t
     }
     const size_t lds_h = replay_scan_lds(R);
     const bool pk = R <= PACKED_REPLAY_MAX_K;
-    if (lds_h > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute(pk ? (const void*)k_list_heap<true> : (const void*)k_list_heap<false>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h));
+    HIPCHK(set_dyn_lds(pk ? (const void*)k_list_heap<true> : (const void*)k_list_heap<false>, lds_h));
     int64_t gi = 0;
     for (const ListGroup& g : plan.groups) {
         const int b = (int)(gi & 1);
@@ -1586,13 +1554,7 @@ int search_hnsw_lists(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t
     for (int b = 0; b < 2 && b < gi; b++) HIPCHK(hipStreamWaitEvent(s, idx->evr[b], 0));
     rc = hnsw_finish(idx, s, nq, R, k, trim, rescore, o_ids, o_d, o_n);
     if (rc) return rc;
-    if (idx->timing) {
-        HIPCHK(hipStreamSynchronize(s));
-        float ms = 0.f;
-        if (gi > 0) hipEventElapsedTime(&ms, idx->ev0, idx->ev1);
-        idx->stats.last_select_ms = ms;
-    }
-    return WV_OK;
+    return read_select_ms(idx, s, gi > 0);
 }
 
 // ---- sharded hnsw flat search over compressed vectors (weaviate_amd/sharded.py
@@ -1655,69 +1617,58 @@ extern "C" int wv_index_quant_max_batch(wv_index* idx, int32_t k, int32_t world,
 // 1: searchByVectorQuantized's rescoring heap)}
 extern "C" int wv_index_quant_begin(wv_index* idx, const float* d_queries, int64_t nq, int64_t d, int32_t k,
                                     int64_t* out, void* stream) {
-    if (!idx || !out) return set_err(WV_ERR_INVALID, "nil argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (nq <= 0) return set_err(WV_ERR_INVALID, "quant_begin: empty batch");
-    if (k <= 0) return set_err(WV_ERR_INVALID, "k must be positive (reference heap Top() on empty queue)");
-    int limit = 0, trim = 0, rescore = 0, comp = 0, form = 0;
-    int rc = quant_params(idx, k, &limit, &trim, &rescore, &form);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    rc = hnsw_prep(idx, s, d_queries, nq, d, k, &limit, &comp);
-    if (rc) return rc;
-    const int64_t ld = std::max<int64_t>(round_up(idx->hiwater, EBLK), EBLK);
-    if (nq * ld * 4 > (16ll << 30))
-        return set_err(WV_ERR_UNSUPPORTED, "quant_begin: %lld queries x %lld rows exceed one 16 GiB distance group",
-                       (long long)nq, (long long)ld);
-    HIPCHK(idx->rE.ensure((size_t)nq * ld * sizeof(float)));
-    HIPCHK(idx->rB.ensure((size_t)nq * (ld / EBLK) * sizeof(float)));
-    if (idx->hiwater > 0) {
-        if (idx->timing) HIPCHK(hipEventRecord(idx->ev0, s));
-        rc = hnsw_dist(idx, s, comp, idx->present, idx->ident.as<int32_t>(), nq, 0, (int)nq, ld, idx->rE.as<float>(),
-                       idx->rB.as<float>());
+    return staged_call(idx, out != nullptr, "nil argument", "quant_begin", nullptr, stream, [&](hipStream_t s) -> int {
+        if (nq <= 0) return set_err(WV_ERR_INVALID, "quant_begin: empty batch");
+        if (k <= 0) return set_err(WV_ERR_INVALID, "k must be positive (reference heap Top() on empty queue)");
+        int limit = 0, trim = 0, rescore = 0, comp = 0, form = 0;
+        int rc = quant_params(idx, k, &limit, &trim, &rescore, &form);
         if (rc) return rc;
-        if (idx->timing) HIPCHK(hipEventRecord(idx->ev1, s));
-        idx->stats.last_group_queries = (uint64_t)nq;
-    } else {
-        // no rows: every block minimum +inf (a finite fill would read as one row's distance)
-        const int64_t nbm = nq * (ld / EBLK);
-        k_fill_u32<<<(unsigned)((nbm + 255) / 256), 256, 0, s>>>(idx->rB.as<uint32_t>(), nbm, 0x7f800000u);
-        HIPCHK(hipGetLastError());
-    }
-    idx->qt_nq = nq;
-    idx->qt_ld = ld;
-    idx->qt_k = k;
-    idx->qt_R = limit;
-    idx->qt_trim = trim;
-    idx->qt_rescore = rescore;
-    idx->qt_comp = comp;
-    idx->qt_form = form;
-    out[0] = limit;
-    out[1] = ld / EBLK;
-    out[2] = rescore;
-    out[3] = form;
-    if (!stream || (idx->timing && idx->hiwater > 0)) HIPCHK(hipStreamSynchronize(s));
-    if (idx->timing && idx->hiwater > 0) {
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, idx->ev0, idx->ev1);
-        idx->stats.last_select_ms = ms;
-    }
-    return WV_OK;
+        rc = hnsw_prep(idx, s, d_queries, nq, d, k, &limit, &comp);
+        if (rc) return rc;
+        const int64_t ld = std::max<int64_t>(round_up(idx->hiwater, EBLK), EBLK);
+        if (nq * ld * 4 > (16ll << 30))
+            return set_err(WV_ERR_UNSUPPORTED, "quant_begin: %lld queries x %lld rows exceed one 16 GiB distance group",
+                           (long long)nq, (long long)ld);
+        HIPCHK(idx->rE.ensure((size_t)nq * ld * sizeof(float)));
+        HIPCHK(idx->rB.ensure((size_t)nq * (ld / EBLK) * sizeof(float)));
+        if (idx->hiwater > 0) {
+            if (idx->timing) HIPCHK(hipEventRecord(idx->ev0, s));
+            rc = hnsw_dist(idx, s, comp, idx->present, idx->ident.as<int32_t>(), nq, 0, (int)nq, ld, idx->rE.as<float>(),
+                           idx->rB.as<float>());
+            if (rc) return rc;
+            if (idx->timing) HIPCHK(hipEventRecord(idx->ev1, s));
+            idx->stats.last_group_queries = (uint64_t)nq;
+        } else {
+            // no rows: every block minimum +inf (a finite fill would read as one row's distance)
+            const int64_t nbm = nq * (ld / EBLK);
+            k_fill_u32<<<(unsigned)((nbm + 255) / 256), 256, 0, s>>>(idx->rB.as<uint32_t>(), nbm, 0x7f800000u);
+            HIPCHK(hipGetLastError());
+        }
+        idx->qt_nq = nq;
+        idx->qt_ld = ld;
+        idx->qt_k = k;
+        idx->qt_R = limit;
+        idx->qt_trim = trim;
+        idx->qt_rescore = rescore;
+        idx->qt_comp = comp;
+        idx->qt_form = form;
+        out[0] = limit;
+        out[1] = ld / EBLK;
+        out[2] = rescore;
+        out[3] = form;
+        return idx->hiwater > 0 ? read_select_ms(idx, s) : WV_OK;  // no rows: no kernel was bracketed
+    });
 }
 
 // the block minima [nq][nblk] (each the compressed distance of one distinct row;
 // the caller's R smallest bound the worker heap across shards)
 extern "C" int wv_index_quant_blockmin(wv_index* idx, float* d_out, void* stream) {
-    if (!idx || !d_out) return set_err(WV_ERR_INVALID, "nil argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (idx->qt_nq <= 0) return set_err(WV_ERR_INVALID, "quant_blockmin: no batch begun");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(d_out, idx->rB.p, (size_t)idx->qt_nq * (idx->qt_ld / EBLK) * sizeof(float),
-                          hipMemcpyDeviceToDevice, s));
-    if (!stream) HIPCHK(hipStreamSynchronize(s));
-    return WV_OK;
+    return staged_call(idx, d_out != nullptr, "nil argument", "quant_blockmin", &wv_index::qt_nq, stream,
+                       [&](hipStream_t s) -> int {
+        HIPCHK(hipMemcpyAsync(d_out, idx->rB.p, (size_t)idx->qt_nq * (idx->qt_ld / EBLK) * sizeof(float),
+                              hipMemcpyDeviceToDevice, s));
+        return WV_OK;
+    });
 }
 
 // the worker heap over this shard in id order from heap states d_in_* ([nq][R]
@@ -1737,37 +1688,26 @@ static int quant_replay(wv_index* idx, hipStream_t s, const uint64_t* in_i, cons
 extern "C" int wv_index_quant_replay(wv_index* idx, const uint64_t* d_in_ids, const float* d_in_d,
                                      const int32_t* d_in_len, int32_t extract, uint64_t* d_out_ids, float* d_out_d,
                                      int32_t* d_out_len, void* stream) {
-    if (!idx || !d_out_ids || !d_out_d || !d_out_len) return set_err(WV_ERR_INVALID, "nil argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (idx->qt_nq <= 0) return set_err(WV_ERR_INVALID, "quant_replay: no batch begun");
-    hipStream_t s = (hipStream_t)stream;
-    int rc = quant_replay(idx, s, d_in_ids, d_in_d, d_in_len, extract ? 1 : 0, d_out_ids, d_out_d, d_out_len, nullptr,
-                          nullptr, nullptr, 0);
-    if (rc) return rc;
-    if (!stream) HIPCHK(hipStreamSynchronize(s));
-    return WV_OK;
+    return staged_call(idx, d_out_ids && d_out_d && d_out_len, "nil argument", "quant_replay", &wv_index::qt_nq, stream,
+                       [&](hipStream_t s) {
+        return quant_replay(idx, s, d_in_ids, d_in_d, d_in_len, extract ? 1 : 0, d_out_ids, d_out_d, d_out_len, nullptr,
+                            nullptr, nullptr, 0);
+    });
 }
 
 extern "C" int wv_index_quant_replay_record(wv_index* idx, const uint64_t* d_in_ids, const float* d_in_d,
                                             const int32_t* d_in_len, int32_t cap, uint64_t* d_rec_ids,
                                             float* d_rec_d, int32_t* d_rec_n, void* stream) {
-    if (!idx) return set_err(WV_ERR_INVALID, "nil index");
-    if (cap < 1 || !d_rec_ids || !d_rec_d || !d_rec_n) return set_err(WV_ERR_INVALID, "invalid record buffers");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (idx->qt_nq <= 0) return set_err(WV_ERR_INVALID, "quant_replay_record: no batch begun");
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nq = idx->qt_nq;
-    const int R = idx->qt_R;
-    HIPCHK(idx->ascI.ensure((size_t)nq * R * sizeof(uint64_t)));  // the state itself is not needed
-    HIPCHK(idx->ascD.ensure((size_t)nq * R * sizeof(float)));
-    HIPCHK(idx->ascN.ensure((size_t)nq * sizeof(int32_t)));
-    int rc = quant_replay(idx, s, d_in_ids, d_in_d, d_in_len, 0, idx->ascI.as<uint64_t>(), idx->ascD.as<float>(),
-                          idx->ascN.as<int32_t>(), d_rec_ids, d_rec_d, d_rec_n, cap);
-    if (rc) return rc;
-    if (!stream) HIPCHK(hipStreamSynchronize(s));
-    return WV_OK;
+    if (idx && (cap < 1 || !d_rec_ids || !d_rec_d || !d_rec_n)) return set_err(WV_ERR_INVALID, "invalid record buffers");
+    return staged_call(idx, true, "nil index", "quant_replay_record", &wv_index::qt_nq, stream, [&](hipStream_t s) -> int {
+        const int64_t nq = idx->qt_nq;
+        const int R = idx->qt_R;
+        HIPCHK(idx->ascI.ensure((size_t)nq * R * sizeof(uint64_t)));  // the state itself is not needed
+        HIPCHK(idx->ascD.ensure((size_t)nq * R * sizeof(float)));
+        HIPCHK(idx->ascN.ensure((size_t)nq * sizeof(int32_t)));
+        return quant_replay(idx, s, d_in_ids, d_in_d, d_in_len, 0, idx->ascI.as<uint64_t>(), idx->ascD.as<float>(),
+                            idx->ascN.as<int32_t>(), d_rec_ids, d_rec_d, d_rec_n, cap);
+    });
 }
 
 // from the whole worker heap (extracted ascending [nq][R], global ids): the
@@ -1777,58 +1717,30 @@ extern "C" int wv_index_quant_replay_record(wv_index* idx, const uint64_t* d_in_
 extern "C" int wv_index_quant_finish(wv_index* idx, const uint64_t* d_asc_ids, const float* d_asc_d,
                                      const int32_t* d_asc_n, uint64_t* d_out_ids, float* d_out_d, int32_t* d_out_n,
                                      uint64_t* d_cand_ids, int32_t* d_cand_n, void* stream) {
-    if (!idx || !d_asc_ids || !d_asc_d || !d_asc_n) return set_err(WV_ERR_INVALID, "nil argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (idx->qt_nq <= 0) return set_err(WV_ERR_INVALID, "quant_finish: no batch begun");
-    if (idx->qt_rescore ? (!d_cand_ids || !d_cand_n) : (!d_out_ids || !d_out_d || !d_out_n))
-        return set_err(WV_ERR_INVALID, "nil output buffer");
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nq = idx->qt_nq;
-    const int R = idx->qt_R;
-    if (idx->qt_form == 1) {  // searchByVectorQuantized: every worker-heap item is a candidate (ascending)
-        HIPCHK(hipMemcpyAsync(d_cand_ids, d_asc_ids, (size_t)nq * R * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_cand_n, d_asc_n, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        if (!stream) HIPCHK(hipStreamSynchronize(s));
-        return WV_OK;
-    }
-    const size_t lds_f = (size_t)R * (sizeof(uint64_t) + sizeof(float)) + 16;
-    if (lds_f > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)k_pq_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-    k_pq_finish<<<(unsigned)nq, 64, lds_f, s>>>(d_asc_ids, d_asc_d, d_asc_n, idx->ident.as<int32_t>(), (int)nq, R,
-                                                idx->qt_k, idx->qt_rescore, idx->id_base, d_out_ids, d_out_d, d_out_n,
-                                                nullptr, d_cand_n, idx->qt_rescore ? idx->qt_trim : 0, d_cand_ids);
-    HIPCHK(hipGetLastError());
-    if (!stream) HIPCHK(hipStreamSynchronize(s));
-    return WV_OK;
+    return staged_call(idx, d_asc_ids && d_asc_d && d_asc_n, "nil argument", "quant_finish", &wv_index::qt_nq, stream,
+                       [&](hipStream_t s) -> int {
+        if (idx->qt_rescore ? (!d_cand_ids || !d_cand_n) : (!d_out_ids || !d_out_d || !d_out_n))
+            return set_err(WV_ERR_INVALID, "nil output buffer");
+        const int64_t nq = idx->qt_nq;
+        const int R = idx->qt_R;
+        if (idx->qt_form == 1) {  // searchByVectorQuantized: every worker-heap item is a candidate (ascending)
+            HIPCHK(hipMemcpyAsync(d_cand_ids, d_asc_ids, (size_t)nq * R * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_cand_n, d_asc_n, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            return WV_OK;
+        }
+        return launch_pq_finish(s, d_asc_ids, d_asc_d, d_asc_n, idx->ident.as<int32_t>(), nq, R, idx->qt_k,
+                                idx->qt_rescore, idx->id_base, d_out_ids, d_out_d, d_out_n, nullptr, d_cand_n,
+                                idx->qt_rescore ? idx->qt_trim : 0, d_cand_ids);
+    });
 }
 
 // exact SingleDist of the candidates this shard holds (others left as they are)
 extern "C" int wv_index_quant_rescore(wv_index* idx, const uint64_t* d_cand_ids, const int32_t* d_cand_n, float* d_E,
                                       void* stream) {
-    if (!idx || !d_cand_ids || !d_cand_n || !d_E) return set_err(WV_ERR_INVALID, "nil argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHK(hipSetDevice(idx->device));
-    if (idx->qt_nq <= 0) return set_err(WV_ERR_INVALID, "quant_rescore: no batch begun");
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nq = idx->qt_nq;
-    const int R = idx->qt_R;
-    const int64_t npairs = nq * R;
-    const float* Qn = idx->qn.as<float>();
-    const int32_t* qlist = idx->ident.as<int32_t>();
-    const bool v5 = idx->variant == WV_VARIANT_AVX512;
-#define WV_RS(M, V) k_rescore_ids<M, V><<<(unsigned)((npairs + 63) / 64), 64, 0, s>>>(idx->X, idx->dpad, Qn, idx->dims, d_cand_ids, d_cand_n, qlist, (int)nq, R, idx->id_base, idx->hiwater, d_E)
-    switch (idx->metric) {
-    case WV_METRIC_L2_SQUARED: if (v5) WV_RS(L2, AVX512); else WV_RS(L2, AVX256); break;
-    case WV_METRIC_DOT: if (v5) WV_RS(DOT, AVX512); else WV_RS(DOT, AVX256); break;
-    case WV_METRIC_COSINE_DOT: if (v5) WV_RS(COSINE, AVX512); else WV_RS(COSINE, AVX256); break;
-    case WV_METRIC_MANHATTAN: WV_RS(MANHATTAN, AVX256); break;
-    default: WV_RS(HAMMING, AVX256); break;
-    }
-#undef WV_RS
-    HIPCHK(hipGetLastError());
-    if (!stream) HIPCHK(hipStreamSynchronize(s));
-    return WV_OK;
+    return staged_call(idx, d_cand_ids && d_cand_n && d_E, "nil argument", "quant_rescore", &wv_index::qt_nq, stream,
+                       [&](hipStream_t s) {
+        return launch_rescore_ids(idx, s, d_cand_ids, d_cand_n, idx->qt_nq, idx->qt_R, d_E);
+    });
 }
 
 // the rescoring heap over the candidates: form 0 = h.rescore (hnsw/search.go:1067-1110),
@@ -1842,26 +1754,16 @@ extern "C" int wv_quant_rescore_final(int32_t device, int32_t form, int64_t nq, 
     if (nq <= 0) return WV_OK;
     if (k <= 0 || R < k || world < 1) return set_err(WV_ERR_INVALID, "quant_rescore_final: invalid k / R / world");
     hipStream_t s = (hipStream_t)stream;
-    std::vector<int32_t> id((size_t)nq);
-    for (int64_t i = 0; i < nq; i++) id[i] = (int32_t)i;
     DBuf ql;
     HIPCHK(ql.ensure((size_t)nq * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(ql.p, id.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (form == 1) {
-        int rc = bq_final(s, nq, R, k, world, id_stride, ql.as<int32_t>(), d_cand_ids, d_cand_n, d_E_all, d_out_ids,
-                          d_out_d, d_out_n, 1);
-        if (rc) return rc;
-    } else {
-        const size_t lds_q = (size_t)(k + 1) * (sizeof(uint64_t) + sizeof(float)) + 16;
-        if (lds_q > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)k_pq_rescore_final, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds_q));
-        k_pq_rescore_final<<<(unsigned)nq, 64, lds_q, s>>>(nullptr, d_E_all, d_cand_n, ql.as<int32_t>(), (int)nq, R, k,
-                                                           0, d_out_ids, d_out_d, d_out_n, d_cand_ids, world, id_stride);
-        HIPCHK(hipGetLastError());
-    }
+    int rc = upload_iota(ql.as<int32_t>(), nq, s);
+    if (rc) return rc;
+    rc = form == 1 ? launch_bq_final(s, nq, R, k, world, id_stride, ql.as<int32_t>(), d_cand_ids, d_cand_n, d_E_all,
+                                     d_out_ids, d_out_d, d_out_n, 1)
+                   : launch_pq_rescore_final(s, nullptr, d_E_all, d_cand_n, ql.as<int32_t>(), nq, R, k, 0, d_out_ids,
+                                             d_out_d, d_out_n, d_cand_ids, world, id_stride);
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));  // ql is freed on return
-    ql.release();
     return WV_OK;
 }
 
@@ -2111,13 +2013,12 @@ bool rq_pqa_route(const wv_index* idx, int64_t nq, int k) {
 template <int NC>
 static void launch_rq8_keys(const RQ8Args& a, unsigned grid, hipStream_t s, int bits) {
     constexpr size_t lds = (size_t)rq8_nbuf(NC) * ((size_t)32 * 64 * NC + 656);  // the ring (k_rq8_keys)
+    // a refused limit is not checked here: the launch then fails, and the caller reads that error
     if (bits == 8) {
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute((const void*)k_rq8_keys<NC, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)set_dyn_lds((const void*)k_rq8_keys<NC, 8>, lds);
         k_rq8_keys<NC, 8><<<grid, 512, lds, s>>>(a);
     } else {
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute((const void*)k_rq8_keys<NC, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)set_dyn_lds((const void*)k_rq8_keys<NC, 1>, lds);
         k_rq8_keys<NC, 1><<<grid, 512, lds, s>>>(a);
     }
 }
@@ -2354,7 +2255,7 @@ static int rq8_replay_list(wv_index* idx, hipStream_t s, const uint32_t* valid, 
     const bool b8 = idx->rq_bits == 8;
     const void* fn = vq > 0 ? (b8 ? (const void*)k_rq8_replay<8, true> : (const void*)k_rq8_replay<1, true>)
                             : (b8 ? (const void*)k_rq8_replay<8> : (const void*)k_rq8_replay<1>);
-    if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(set_dyn_lds(fn, lds));
     const void* qsrc = b8 ? (const void*)idx->rq8Qp.p : idx->rqq.p;
 #define WV_RQR(B, PQV)                                                                                             \
     k_rq8_replay<B, PQV><<<(unsigned)n, 512, lds, s>>>(idx->qsKey.as<float>(), nblk, nblk, idx->rq_codes, idx->cap, \
@@ -2397,12 +2298,8 @@ int search_rq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
     if (rc) return rc;
     idx->stats.queries += (uint64_t)nq;
     idx->stats.batches++;
-    HIPCHK(idx->ident.ensure((size_t)nq * sizeof(int32_t)));
-    {
-        std::vector<int32_t> id((size_t)nq);
-        for (int64_t i = 0; i < nq; i++) id[i] = (int32_t)i;
-        HIPCHK(hipMemcpyAsync(idx->ident.p, id.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    }
+    rc = ensure_ident(idx, nq, s);
+    if (rc) return rc;
     HIPCHK(idx->ascI.ensure((size_t)nq * R * sizeof(uint64_t)));
     HIPCHK(idx->ascD.ensure((size_t)nq * R * sizeof(float)));
     HIPCHK(idx->ascN.ensure((size_t)nq * sizeof(int32_t)));
@@ -2424,7 +2321,7 @@ int search_rq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
     if (!mfma) {
         rc = rq_replay(idx, s, valid, R, nullptr, nq);
         if (rc) return rc;
-        rc = bq_rescore(idx, s, idx->ascI.as<uint64_t>(), idx->ascN.as<int32_t>(), idx->candE.as<float>());
+        rc = launch_rescore_ids(idx, s, idx->ascI.as<uint64_t>(), idx->ascN.as<int32_t>(), nq, R, idx->candE.as<float>());
         if (rc) return rc;
     } else {
         rc = rq8_candidates(idx, s, nq, R, valid, own, own_vq);
@@ -2433,7 +2330,7 @@ int search_rq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
         // oF: 1 = replayed, 2 = decided by the rescored distances (k_rq_tiecheck:
         // 3 replayed, else 0).  Every row is rescored first (replayed rows hold
         // no candidates yet), then the replayed queries' rows once more.
-        rc = bq_rescore(idx, s, idx->ascI.as<uint64_t>(), idx->ascN.as<int32_t>(), idx->candE.as<float>());
+        rc = launch_rescore_ids(idx, s, idx->ascI.as<uint64_t>(), idx->ascN.as<int32_t>(), nq, R, idx->candE.as<float>());
         if (rc) return rc;
         k_rq_tiecheck<<<(unsigned)((nq + 3) / 4), 256, 0, s>>>(idx->candE.as<float>(), idx->ascN.as<int32_t>(), (int)nq,
                                                                R, k, idx->oF.as<int32_t>());
@@ -2450,36 +2347,14 @@ int search_rq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
         if (cnt[1] > 0) {
             rc = rq8_replay_list(idx, s, own ? own : valid, R, list, cnt[1], nq, own_vq);
             if (rc) return rc;
-            const int64_t np = (int64_t)cnt[1] * R;
-            const bool v5 = idx->variant == WV_VARIANT_AVX512;
-#define WV_RSL(M, V)                                                                                                 \
-    k_rescore_list<M, V><<<(unsigned)((np + 63) / 64), 64, 0, s>>>(idx->X, idx->dpad, idx->qn.as<float>(), idx->dims,  \
-                                                                   idx->ascI.as<uint64_t>(), idx->ascN.as<int32_t>(), \
-                                                                   list, (int)cnt[1], R, idx->id_base, idx->hiwater,  \
-                                                                   idx->candE.as<float>())
-            switch (idx->metric) {
-            case WV_METRIC_L2_SQUARED: if (v5) WV_RSL(L2, AVX512); else WV_RSL(L2, AVX256); break;
-            case WV_METRIC_DOT: if (v5) WV_RSL(DOT, AVX512); else WV_RSL(DOT, AVX256); break;
-            default: if (v5) WV_RSL(COSINE, AVX512); else WV_RSL(COSINE, AVX256); break;
-            }
-#undef WV_RSL
-            HIPCHK(hipGetLastError());
+            rc = launch_rescore_list(idx, s, list, (int)cnt[1], R);
+            if (rc) return rc;
         }
     }
-    const int32_t* qlist = idx->ident.as<int32_t>();
-    const size_t lds_f = (size_t)k * (sizeof(uint64_t) + sizeof(float)) + 16;
-    if (lds_f > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void*)k_bq_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-    k_bq_final<<<(unsigned)nq, 64, lds_f, s>>>(idx->ascI.as<uint64_t>(), idx->candE.as<float>(), idx->ascN.as<int32_t>(),
-                                               qlist, (int)nq, R, k, 1, 0, o_ids, o_d, o_n, 1);
-    HIPCHK(hipGetLastError());
-    if (idx->timing) {
-        HIPCHK(hipStreamSynchronize(s));
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, idx->ev0, idx->ev1);
-        idx->stats.last_select_ms = ms;
-    }
-    return WV_OK;
+    rc = launch_bq_final(s, nq, R, k, 1, 0, idx->ident.as<int32_t>(), idx->ascI.as<uint64_t>(), idx->ascN.as<int32_t>(),
+                         idx->candE.as<float>(), o_ids, o_d, o_n, 1);
+    if (rc) return rc;
+    return read_select_ms(idx, s);
 }
 
 extern "C" int wv_index_rq_info(wv_index* idx, int32_t* out) {

@@ -9,7 +9,7 @@
 template <int NP, int BITS>
 static hipError_t launch_rq8_keys_cp(const RQ8Args& a, hipStream_t s) {
     constexpr int lds = RQ8_CP_NBUF * RQ8_CP_SLOT;  // the ring: above 64 KiB
-    hipError_t e = hipFuncSetAttribute((const void*)k_rq8_keys_cp<NP, BITS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipError_t e = (hipError_t)set_dyn_lds((const void*)k_rq8_keys_cp<NP, BITS>, lds);
     if (e != hipSuccess) return e;
     k_rq8_keys_cp<NP, BITS><<<(unsigned)(a.nqg * a.nspans), 64 * rq8_cp_waves(NP), lds, s>>>(a);
     return hipGetLastError();

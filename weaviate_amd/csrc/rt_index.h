@@ -31,6 +31,7 @@
 #include "key_plan.h"
 #include "list_plan.h"
 #include "pqa_plan.h"
+#include "dyn_lds.h"
 #include "kernels.hip"
 #include "l1_kernels.hip"
 #include "bq_kernels.hip"
@@ -66,7 +67,7 @@ constexpr bool BQ_PACK_AUTO_25_32 = true, BQ_PACK_AUTO_33_64 = true;
 
 #define HIPCHK(x)                                                                              \
     do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
+        hipError_t e_ = (hipError_t)(x); /* a hipError_t, or one held in an int (set_dyn_lds) */ \
         if (e_ != hipSuccess) return set_err(WV_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); \
     } while (0)
 
@@ -104,6 +105,26 @@ static inline bool metric_bilinear(int m) {
 // pq_kernels.hip); cap is a multiple of 256
 static inline int64_t pq_mwp(int m) { return (int64_t)((m + 15) / 16) * 4; }
 static inline int pq_g16(int m) { return (m + 15) / 16; }
+
+// f(metric tag, variant tag), std::integral_constants of wv::Metric / wv::Variant, for a kernel templated on
+// both.  The bilinear form is for sites that only bilinear metrics reach; default: cosine, as their switches had it.
+template <class F>
+static inline void for_bilinear_variant(int metric, int variant, F&& f) {
+    auto both = [&](auto m) {
+        if (variant == WV_VARIANT_AVX512) f(m, std::integral_constant<int, AVX512>{});
+        else f(m, std::integral_constant<int, AVX256>{});
+    };
+    if (metric == WV_METRIC_L2_SQUARED) both(std::integral_constant<int, L2>{});
+    else if (metric == WV_METRIC_DOT) both(std::integral_constant<int, DOT>{});
+    else both(std::integral_constant<int, COSINE>{});
+}
+// every metric: manhattan and hamming have the AVX256 summation order only
+template <class F>
+static inline void for_metric_variant(int metric, int variant, F&& f) {
+    if (metric_bilinear(metric)) for_bilinear_variant(metric, variant, f);
+    else if (metric == WV_METRIC_MANHATTAN) f(std::integral_constant<int, MANHATTAN>{}, std::integral_constant<int, AVX256>{});
+    else f(std::integral_constant<int, HAMMING>{}, std::integral_constant<int, AVX256>{});
+}
 
 struct wv_batcher;
 static void batcher_free(wv_index* idx, wv_batcher* b);
@@ -358,6 +379,29 @@ static void invalidate_batch(wv_index* idx) {
     idx->bq_nq = 0;  // a sharded BQ batch's minima and query rows (wv_index_bq_begin)
 }
 
+// id[i] = i for i < n on the device (the pageable source is staged before the copy returns)
+static inline int upload_iota(int32_t* d, int64_t n, hipStream_t s) {
+    std::vector<int32_t> id((size_t)n);
+    std::iota(id.begin(), id.end(), 0);
+    HIPCHK(hipMemcpyAsync(d, id.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    return WV_OK;
+}
+// the identity query list of a batch of nq in idx->ident
+static inline int ensure_ident(wv_index* idx, int64_t nq, hipStream_t s) {
+    HIPCHK(idx->ident.ensure((size_t)nq * sizeof(int32_t)));
+    return upload_iota(idx->ident.as<int32_t>(), nq, s);
+}
+// option timing: wait for s and store the ev0 / ev1 bracket as last_select_ms
+// (0 when this batch recorded none)
+static inline int read_select_ms(wv_index* idx, hipStream_t s, bool recorded = true) {
+    if (!idx->timing) return WV_OK;
+    HIPCHK(hipStreamSynchronize(s));
+    float ms = 0.f;
+    if (recorded) hipEventElapsedTime(&ms, idx->ev0, idx->ev1);
+    idx->stats.last_select_ms = ms;
+    return WV_OK;
+}
+
 // ---------------------------------------------------------------------------
 // create / destroy / capacity
 // ---------------------------------------------------------------------------
@@ -432,6 +476,29 @@ int launch_blk_replay(wv_index* idx, hipStream_t s, const float* key, int64_t ld
                       int extract, int by_list, uint64_t* rec_i = nullptr, float* rec_d = nullptr,
                       int32_t* rec_n = nullptr, int rec_cap = 0);
 // quant_runtime.hip
+// The final-stage launchers: each of these kernels is launched from its
+// launcher only, which sizes the dynamic LDS and raises the limit for it.
+// k_bq_final: insertToHeap(heap, k, ...) in pop order (asc = 1: candidates ascending) + extractHeap
+int launch_bq_final(hipStream_t s, int64_t nq, int R, int k, int world, uint64_t id_stride, const int32_t* qlist,
+                    const uint64_t* ids, const int32_t* cnt, const float* E, uint64_t* o_ids, float* o_d, int32_t* o_n,
+                    int asc = 0);
+// k_pq_finish: the worker heaps' ascending extractions [nq][R] -> the result heap (rescore == 0) or the
+// candidates after the trim, as slots (cand_slot) or global ids (cand_ids)
+int launch_pq_finish(hipStream_t s, const uint64_t* asc_ids, const float* asc_d, const int32_t* asc_n,
+                     const int32_t* qlist, int64_t nq, int R, int k, int rescore, uint64_t id_base, uint64_t* o_ids,
+                     float* o_d, int32_t* o_n, uint32_t* cand_slot, int32_t* cand_n, int trim,
+                     uint64_t* cand_ids = nullptr);
+// k_pq_rescore_final: h.rescore's heap over the rescored candidates
+int launch_pq_rescore_final(hipStream_t s, const uint32_t* cand_slot, const float* E, const int32_t* cand_n,
+                            const int32_t* qlist, int64_t nq, int R, int k, uint64_t id_base, uint64_t* o_ids,
+                            float* o_d, int32_t* o_n, const uint64_t* cand_ids = nullptr, int world = 1,
+                            uint64_t id_stride = 0);
+// exact SingleDist of [nq][R] candidates of the prepared queries (idx->qn): by slot (k_rescore), by global id
+// with counts (k_rescore_ids), or the rows of the listed queries of ascI / ascN into candE (k_rescore_list)
+int launch_rescore_slots(wv_index* idx, hipStream_t s, const uint32_t* slots, int64_t nq, int R, float* E);
+int launch_rescore_ids(wv_index* idx, hipStream_t s, const uint64_t* ids, const int32_t* cnt, int64_t nq, int R,
+                       float* E);
+int launch_rescore_list(wv_index* idx, hipStream_t s, const int32_t* list, int nlist, int R);
 int search_bq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k, const uint32_t* valid,
               uint64_t* o_ids, float* o_d, int32_t* o_n);
 int search_rq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k, const uint32_t* valid,

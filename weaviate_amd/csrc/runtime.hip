@@ -1126,12 +1126,12 @@ static int search_core(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
         if (idx->timing) HIPCHK(hipEventRecord(idx->ev0, s));
 #define WV_SEL3(M)                                                                                        \
     do {                                                                                                  \
-        HIPCHK(hipFuncSetAttribute((const void*)k_mfma_select3<M, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        HIPCHK(set_dyn_lds((const void*)k_mfma_select3<M, 1>, lds));                                      \
         k_mfma_select3<M, 1><<<grid, 512, lds, s>>>(a);                                                   \
     } while (0)
 #define WV_GEMV(M, G)                                                                                      \
     do {                                                                                                   \
-        HIPCHK(hipFuncSetAttribute((const void*)k_gemv_select<M, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        HIPCHK(set_dyn_lds((const void*)k_gemv_select<M, G>, lds));                                        \
         k_gemv_select<M, G><<<grid, 256, lds, s>>>(a);                                                     \
     } while (0)
 #define WV_GEMVQ(M)                                          \
@@ -1177,15 +1177,9 @@ static int search_core(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
         else
             k_merge_spans<1><<<(unsigned)((nq + 3) / 4), 256, 0, s>>>(a.outA, a.outI, (int)nq, (int)nspans, KP,
                                                                        idx->candA.as<float>(), idx->candI.as<uint32_t>());
-        const int64_t npairs = nq * KP;
-        const bool v5 = idx->variant == WV_VARIANT_AVX512;
-#define WV_RS(M, V) k_rescore<M, V><<<(unsigned)((npairs + 63) / 64), 64, 0, s>>>(idx->X, idx->dpad, Qn, idx->dims, idx->candI.as<uint32_t>(), (int)nq, KP, idx->candE.as<float>())
-        switch (idx->metric) {
-        case WV_METRIC_L2_SQUARED: if (v5) WV_RS(L2, AVX512); else WV_RS(L2, AVX256); break;
-        case WV_METRIC_DOT: if (v5) WV_RS(DOT, AVX512); else WV_RS(DOT, AVX256); break;
-        default: if (v5) WV_RS(COSINE, AVX512); else WV_RS(COSINE, AVX256); break;
-        }
-#undef WV_RS
+        // only l2-squared / dot / cosine arrive here: mfma_ok admits bilinear metrics only
+        rc = launch_rescore_slots(idx, s, idx->candI.as<uint32_t>(), nq, KP, idx->candE.as<float>());
+        if (rc) return rc;
         // error bound of |A - E|: 2 gamma_{d+4} * bound, +5% slack
         uint32_t mx = 0;
         HIPCHK(hipMemcpyAsync(&mx, idx->d_maxn2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));

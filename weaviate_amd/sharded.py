@@ -278,24 +278,19 @@ class GpuBQShardBackend(GpuShardBackend):
         return oi, od, on
 
 
-class ShardedBQSearch:
-    """BQ-compressed search over contiguous id-range shards (one per rank) with
-    the single index's exact semantics (flat/index.go:460-532):
-      1. every rank: query codes + hamming block minima of its shard (parallel,
-         the expensive VALU pass);
-      2. the R-heap over all shards in id order, in one parallel hop (backends
-         with bq_replay_record): each rank's R smallest block minima are
-         all-gathered; rank r >= 1 replays its range from R copies of T_r (the
-         R-th smallest minimum of the ranks before it: distances of distinct
-         rows, so T_r >= the real heap top at its first row) and records every
-         insertion; rank 0 replays from empty heaps; one all-gather of the
-         records, and every rank applies them on rank 0's states in rank
-         order (wv_heap_merge_records) -- the serial chain's heaps.  A record
-         that overflows its cap sends the batch down the serial chain (rank r
-         continues rank r-1's heap states, one broadcast per hop);
-      3. every rank rescores the candidates it holds (exact SingleDist) in the
-         reference's pop order, all-gather of the [B][R] distance tiles;
-      4. the rescoring heap (insertToHeap in pop order, extractHeap)."""
+class _ShardedRHeap:
+    """The R-heap over contiguous id-range shards (one per rank) in id order,
+    shared by ShardedBQSearch and ShardedQuantSearch.  Every rank has begun the
+    batch (its block minima exist); then, in one parallel hop (_rheap_parallel):
+    each rank's R smallest block minima are all-gathered; rank r >= 1 replays
+    its range from R copies of T_r (the R-th smallest minimum of the ranks
+    before it: distances of distinct rows, so T_r >= the real heap top at its
+    first row) and records every insertion; rank 0 replays from empty heaps;
+    one all-gather of the records, and every rank applies them on rank 0's
+    states in rank order (wv_heap_merge_records) -- the serial chain's heaps.
+    A record that overflows its cap sends the batch down the serial chain
+    (_rheap_chain: rank r continues rank r-1's heap states, one broadcast per
+    hop)."""
 
     def __init__(self, backend, device: torch.device, id_stride: int):
         self.b = backend
@@ -306,6 +301,60 @@ class ShardedBQSearch:
 
     def _all_gather(self, t: torch.Tensor) -> torch.Tensor:
         return ShardedFlatSearch._all_gather(self, t)
+
+    def _rheap_parallel(self, nq: int, R: int, cap: int, bounds, replay, replay_record):
+        """-> the merged heaps extracted ascending (ids, dists, lengths), or None
+        when a record of `cap` entries overflowed (host sync: one flag).
+        bounds() / replay(state, extract) / replay_record(state, cap): the backend's."""
+        G = self._all_gather(bounds())  # [W, nq, R]
+        if self.rank == 0:
+            ti, td, tn = replay(None, False)  # heap states from empty heaps
+            ri = torch.zeros((nq, cap), dtype=torch.int64, device=self.dev)
+            rd = torch.zeros((nq, cap), dtype=torch.float32, device=self.dev)
+            ri[:, :R], rd[:, :R] = ti, td
+            rn = tn
+        else:
+            allq = torch.arange(nq, device=self.dev)
+            T = prefix_bound(self.rank, allq, R, G, torch.full((self.rank, nq), R, dtype=torch.int32, device=self.dev),
+                             torch.zeros((self.rank, nq), dtype=torch.int32, device=self.dev))
+            ri, rd, rn = replay_record(fake_heaps(T, R), cap)
+        pk = torch.cat([ri.contiguous().view(torch.int32).reshape(nq, 2 * cap), rd.contiguous().view(torch.int32),
+                        rn[:, None]], 1)
+        A = self._all_gather(pk)  # [W, nq, 3 cap + 1]
+        rec = (A[..., : 2 * cap].contiguous().view(torch.int64), A[..., 2 * cap: 3 * cap].contiguous().view(torch.float32),
+               A[..., 3 * cap].contiguous())
+        st = (rec[0][0, :, :R].contiguous(), rec[1][0, :, :R].contiguous(), rec[2][0].contiguous())
+        ai, ad, an, un = self.b.merge_records(self.world, R, cap, st, rec)  # extracted ascending
+        if bool(un.any()):
+            return None
+        return ai, ad, an
+
+    def _rheap_chain(self, nq: int, R: int, replay):
+        """The serial chain: rank r continues rank r-1's heaps; the last rank's
+        replay(state, True) ends it (BQ: pops, quant: extracts ascending).  -> its state."""
+        state = None
+        for r in range(self.world):
+            last = r == self.world - 1
+            if self.rank == r:  # one packed broadcast per hop: [nq][2R ids | R dists | len]
+                buf = ShardedFlatSearch._pack_state(*replay(state, last))
+            else:
+                buf = torch.empty((nq, 3 * R + 1), dtype=torch.int32, device=self.dev)
+            dist.broadcast(buf, src=r)
+            state = ShardedFlatSearch._unpack_state(buf, R)
+        return state
+
+
+class ShardedBQSearch(_ShardedRHeap):
+    """BQ-compressed search over contiguous id-range shards (one per rank) with
+    the single index's exact semantics (flat/index.go:460-532):
+      1. every rank: query codes + hamming block minima of its shard (parallel,
+         the expensive VALU pass);
+      2. the R-heap over all shards in id order (_ShardedRHeap): in one parallel
+         hop for backends with bq_replay_record, else, or when a record
+         overflows, down the serial chain;
+      3. every rank rescores the candidates it holds (exact SingleDist) in the
+         reference's pop order, all-gather of the [B][R] distance tiles;
+      4. the rescoring heap (insertToHeap in pop order, extractHeap)."""
 
     def search(self, q: torch.Tensor, k: int):
         nq = q.shape[0]
@@ -323,46 +372,19 @@ class ShardedBQSearch:
         return self._chain(q, nq, R)
 
     def _replay_parallel(self, nq: int, R: int):
-        """Step 2 in one hop; -> (candidate ids in pop order [nq, R], lengths)
-        or None when a record overflowed (host sync: one flag)."""
-        cap = 2 * R
-        G = self._all_gather(self.b.bq_bounds())  # [W, nq, R]
-        if self.rank == 0:
-            ti, td, tn = self.b.bq_replay(None, False)  # heap states from empty heaps
-            ri = torch.zeros((nq, cap), dtype=torch.int64, device=self.dev)
-            rd = torch.zeros((nq, cap), dtype=torch.float32, device=self.dev)
-            ri[:, :R], rd[:, :R] = ti, td
-            rn = tn
-        else:
-            allq = torch.arange(nq, device=self.dev)
-            T = prefix_bound(self.rank, allq, R, G, torch.full((self.rank, nq), R, dtype=torch.int32, device=self.dev),
-                             torch.zeros((self.rank, nq), dtype=torch.int32, device=self.dev))
-            ri, rd, rn = self.b.bq_replay_record(fake_heaps(T, R), cap)
-        pk = torch.cat([ri.contiguous().view(torch.int32).reshape(nq, 2 * cap), rd.contiguous().view(torch.int32),
-                        rn[:, None]], 1)
-        A = self._all_gather(pk)  # [W, nq, 3 cap + 1]
-        rec = (A[..., : 2 * cap].contiguous().view(torch.int64), A[..., 2 * cap: 3 * cap].contiguous().view(torch.float32),
-               A[..., 3 * cap].contiguous())
-        st = (rec[0][0, :, :R].contiguous(), rec[1][0, :, :R].contiguous(), rec[2][0].contiguous())
-        ai, _, an, un = self.b.merge_records(self.world, R, cap, st, rec)  # extracted ascending
-        if bool(un.any()):
+        """Step 2 in one hop (records of 2R entries); -> (candidate ids in pop
+        order [nq, R], lengths) or None when a record overflowed."""
+        res = self._rheap_parallel(nq, R, 2 * R, self.b.bq_bounds, self.b.bq_replay, self.b.bq_replay_record)
+        if res is None:
             return None
+        ai, _, an = res
         # pop order (max first) = the ascending extraction read back to front
         back = (an[:, None].long() - 1 - torch.arange(R, device=self.dev)[None, :]).clamp(min=0)
         return ai.gather(1, back), an
 
     def _chain(self, q: torch.Tensor, nq: int, R: int):
-        """Step 2 as the serial chain: rank r continues rank r-1's heaps."""
-        state = None
-        for r in range(self.world):
-            last = r == self.world - 1
-            if self.rank == r:  # one packed broadcast per hop: [nq][2R ids | R dists | len]
-                buf = ShardedFlatSearch._pack_state(*self.b.bq_replay(state, last))
-            else:
-                buf = torch.empty((nq, 3 * R + 1), dtype=torch.int32, device=self.dev)
-            dist.broadcast(buf, src=r)
-            state = ShardedFlatSearch._unpack_state(buf, R)
-        ids, _, ln = state
+        """Step 2 as the serial chain (the last rank pops), then steps 3 and 4."""
+        ids, _, ln = self._rheap_chain(nq, R, self.b.bq_replay)
         E = self.b.bq_rescore(ids, ln)
         E_all = self._all_gather(E)
         return self.b.bq_final(self.world, self.id_stride, ids, ln, E_all)
@@ -456,7 +478,7 @@ class GpuQuantShardBackend(GpuShardBackend):
         return oi, od, on
 
 
-class ShardedQuantSearch:
+class ShardedQuantSearch(_ShardedRHeap):
     """hnsw's flat search over compressed vectors (trained PQ, SQ;
     hnsw/flat_search.go:28-141 + h.rescore, hnsw/search.go:1047-1110) and
     flat's searchByVectorQuantized over rq-8 / rq-1 codes
@@ -464,26 +486,11 @@ class ShardedQuantSearch:
     contiguous id-range shards with the single index's exact semantics:
       1. every rank: the compressed distances of its rows to the batch and
          their 256-row block minima (wv_index_quant_begin, parallel);
-      2. the worker heap (limit R) over all shards in id order in one parallel
-         hop, BQ's record scheme (ShardedBQSearch): the R smallest block minima
-         of each rank are all-gathered; rank r >= 1 replays from R copies of
-         T_r and records its insertions; rank 0 replays from empty heaps; the
-         records are all-gathered and merged on rank 0's states
-         (wv_heap_merge_records).  A record over its cap sends the batch down
-         the serial chain;
+      2. the worker heap (limit R) over all shards in id order (_ShardedRHeap):
+         in one parallel hop, or, when a record overflows, down the serial chain;
       3. the result heap in pop order; with rescoring, every rank computes the
          exact distances of the candidates it holds, one all-gather, and
          h.rescore picks each candidate's distance from its owner."""
-
-    def __init__(self, backend, device: torch.device, id_stride: int):
-        self.b = backend
-        self.dev = device
-        self.rank = dist.get_rank()
-        self.world = dist.get_world_size()
-        self.id_stride = int(id_stride)
-
-    def _all_gather(self, t: torch.Tensor) -> torch.Tensor:
-        return ShardedFlatSearch._all_gather(self, t)
 
     def search(self, q: torch.Tensor, k: int):
         """Query chunks that every rank's distance group holds (one all-reduce
@@ -520,46 +527,15 @@ class ShardedQuantSearch:
 
     def _replay_parallel(self, nq: int, R: int):
         """Step 2 in one hop; -> the merged worker heaps extracted ascending, or
-        None when a record overflowed (host sync: one flag).  A small worker
-        heap (PQ without rescoring: R = k) records a few dozen insertions
-        beyond R on a shard holding that many rows under T_r: cap = 2R + 64."""
-        cap = 2 * R + 64
-        G = self._all_gather(self.b.quant_bounds())  # [W, nq, R]
-        if self.rank == 0:
-            ti, td, tn = self.b.quant_replay(None, False)  # heap states from empty heaps
-            ri = torch.zeros((nq, cap), dtype=torch.int64, device=self.dev)
-            rd = torch.zeros((nq, cap), dtype=torch.float32, device=self.dev)
-            ri[:, :R], rd[:, :R] = ti, td
-            rn = tn
-        else:
-            allq = torch.arange(nq, device=self.dev)
-            T = prefix_bound(self.rank, allq, R, G, torch.full((self.rank, nq), R, dtype=torch.int32, device=self.dev),
-                             torch.zeros((self.rank, nq), dtype=torch.int32, device=self.dev))
-            ri, rd, rn = self.b.quant_replay_record(fake_heaps(T, R), cap)
-        pk = torch.cat([ri.contiguous().view(torch.int32).reshape(nq, 2 * cap), rd.contiguous().view(torch.int32),
-                        rn[:, None]], 1)
-        A = self._all_gather(pk)  # [W, nq, 3 cap + 1]
-        rec = (A[..., : 2 * cap].contiguous().view(torch.int64), A[..., 2 * cap: 3 * cap].contiguous().view(torch.float32),
-               A[..., 3 * cap].contiguous())
-        st = (rec[0][0, :, :R].contiguous(), rec[1][0, :, :R].contiguous(), rec[2][0].contiguous())
-        ai, ad, an, un = self.b.merge_records(self.world, R, cap, st, rec)  # extracted ascending
-        if bool(un.any()):
-            return None
-        return ai, ad, an
+        None when a record overflowed.  A small worker heap (PQ without
+        rescoring: R = k) records a few dozen insertions beyond R on a shard
+        holding that many rows under T_r: cap = 2R + 64."""
+        return self._rheap_parallel(nq, R, 2 * R + 64, self.b.quant_bounds, self.b.quant_replay,
+                                    self.b.quant_replay_record)
 
     def _chain(self, nq: int, R: int):
-        """Step 2 as the serial chain: rank r continues rank r-1's heaps; the
-        last rank extracts (ascending)."""
-        state = None
-        for r in range(self.world):
-            last = r == self.world - 1
-            if self.rank == r:  # one packed broadcast per hop: [nq][2R ids | R dists | len]
-                buf = ShardedFlatSearch._pack_state(*self.b.quant_replay(state, last))
-            else:
-                buf = torch.empty((nq, 3 * R + 1), dtype=torch.int32, device=self.dev)
-            dist.broadcast(buf, src=r)
-            state = ShardedFlatSearch._unpack_state(buf, R)
-        return state
+        """Step 2 as the serial chain; the last rank extracts (ascending)."""
+        return self._rheap_chain(nq, R, self.b.quant_replay)
 
 
 class ShardedFlatSearch:
