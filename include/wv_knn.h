@@ -630,6 +630,7 @@ typedef struct wv_stats {
 #define WV_ROUTE_L1_TILE 11  /* manhattan: k_l1_rows (register-tiled exact L1 of every row, then the heap replay) */
 #define WV_ROUTE_LIST_SCAN 12 /* hnsw flat search in list order: k_list_dist + k_list_heap over the allow lists' entries */
 #define WV_ROUTE_BQ_PACKED 13 /* BQ block minima: k_bq_packmin (integer MFMA over the packed codes, <= 64 words) */
+#define WV_ROUTE_SQ_INT8 14   /* hnsw flat search over SQ: k_sq_keys (exact SQ block minima on the integer MFMA, d <= 1024) */
 int wv_index_stats(wv_index *idx, wv_stats *out);
 
 /* Diagnostic hook (tests): the last MFMA batch's candidates [nq][KP]:
@@ -665,6 +666,10 @@ int wv_index_debug_bqmin(wv_index *idx, int64_t q, float *mins, int64_t *nblk, i
  * "rq_wide" (flat rq-8 / rq-1 above 1024 rotated dims, up to 4096, on the
  * integer-MFMA route, k_rq8_keys_cp: 1 = always, 0 = never (the
  * distance-matrix route), -1 = auto, the default: rq-1 only),
+ * "sq_keys" (wv_index_hnsw_flat_search over SQ, up to 1024 dims, by exact
+ * block minima on the integer MFMA, k_sq_keys: 1 = wherever eligible, 0 = never
+ * (the distance-matrix route), -1 = auto, the default; WV_ROUTE_SQ_INT8,
+ * DESIGN.md §3.10c),
  * "bq_fast" (1 = BQ queries whose rescored result no hamming tie can change
  * skip the R-heap replay, k_bq_fast; default 0: slower on C4),
  * "exact_bm" / "exact_cap"

@@ -879,8 +879,10 @@ static int sq_encode_queries(wv_index* idx, hipStream_t s, int64_t nq) {
 // the compressed distances E[f][row] (+inf for invalid rows) and their 256-row
 // block minima of listed queries [g0, g0 + F) (PQ: qlist positions; the
 // thread-per-row SQ / RQ / BQ kernels index the query batch directly)
+// sq_listed: the SQ codes of the listed queries were gathered into sq8Fq /
+// sq8Fm by list position (sq8_gather)
 static int hnsw_dist(wv_index* idx, hipStream_t s, int comp, const uint32_t* valid, const int32_t* qlist, int64_t nq,
-                     int64_t g0, int F, int64_t ld, float* E, float* Bm) {
+                     int64_t g0, int F, int64_t ld, float* E, float* Bm, bool sq_listed = false) {
     const int64_t nslots = idx->hiwater;
     const int wrapm = idx->metric == WV_METRIC_L2_SQUARED ? L2 : idx->metric == WV_METRIC_DOT ? DOT : COSINE;
     int rc = WV_OK;
@@ -911,7 +913,8 @@ static int hnsw_dist(wv_index* idx, hipStream_t s, int comp, const uint32_t* val
     } else if (comp == WV_COMPRESSION_SQ) {
         dim3 grid((unsigned)((F + RQ_QPB - 1) / RQ_QPB), (unsigned)(ld / 256));
         k_sq_dist<<<grid, 256, 0, s>>>(idx->sq_codes, idx->sq_meta, idx->sq_Dq, valid, nslots,
-                                       idx->sqq.as<uint4>(), idx->sqm.as<uint2>(), g0, F, wrapm, idx->sq_a2,
+                                       (sq_listed ? idx->sq8Fq : idx->sqq).as<uint4>(),
+                                       (sq_listed ? idx->sq8Fm : idx->sqm).as<uint2>(), g0, F, wrapm, idx->sq_a2,
                                        idx->sq_ab, idx->sq_ib2, ld, E, Bm);
     } else {  // BQ
         dim3 grid((unsigned)((F + RQ_QPB - 1) / RQ_QPB), (unsigned)(ld / 256));
@@ -1219,8 +1222,15 @@ static int search_hnsw(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
     int64_t nrep = nq;
     int rep_by_query = 0;
     const bool pq8 = comp == WV_COMPRESSION_PQ && pq8_route(idx, R, nq);
-    if (pq8 || (comp == WV_COMPRESSION_PQ && idx->pq_cand && R + 1 <= 64)) {
-      if (pq8) {
+    const bool sq8 = comp == WV_COMPRESSION_SQ && sq8_route(idx, R, nq);
+    if (pq8 || sq8 || (comp == WV_COMPRESSION_PQ && idx->pq_cand && R + 1 <= 64)) {
+      if (sq8) {
+        // exact SQ block minima on the integer matrix cores (sq_mfma.hip)
+        HIPCHK(idx->qsList.ensure((size_t)nq * sizeof(int32_t)));
+        HIPCHK(idx->flCtr.ensure(2 * sizeof(uint32_t)));
+        rc = sq8_candidates(idx, s, nq, R, valid);
+        if (rc) return rc;
+      } else if (pq8) {
         rc = pq8_candidates(idx, s, nq, R, valid);
         if (rc) return rc;
       } else {
@@ -1308,6 +1318,10 @@ static int search_hnsw(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
         rep_by_query = 1;
         qlist = idx->qsList.as<int32_t>();
         idx->stats.replayed_queries += nf;
+        if (sq8) {  // k_sq_dist reads its queries by position: the flagged ones as a compact group
+            rc = sq8_gather(idx, s, qlist, nf);
+            if (rc) return rc;
+        }
     } else if (comp == WV_COMPRESSION_PQ) {
         idx->stats.replayed_queries += (uint64_t)nq;
     }
@@ -1341,7 +1355,7 @@ static int search_hnsw(wv_index* idx, hipStream_t s, const float* d_qraw, int64_
         if (gi >= 2) HIPCHK(hipStreamWaitEvent(s, idx->evr[b], 0));
         const bool time_it = idx->timing && g0 == 0 && !rep_by_query;
         if (time_it) HIPCHK(hipEventRecord(idx->ev0, s));
-        rc = hnsw_dist(idx, s, comp, valid, qlist, nq, g0, F, ld, E, Bm);
+        rc = hnsw_dist(idx, s, comp, valid, qlist, nq, g0, F, ld, E, Bm, sq8);
         if (rc) return rc;
         HIPCHK(hipGetLastError());
         if (time_it) HIPCHK(hipEventRecord(idx->ev1, s));
@@ -1790,6 +1804,7 @@ static int sq_set(wv_index* idx, float a, float b) {
         HIPCHK(hipMemsetAsync(idx->sq_meta, 0, (size_t)idx->cap * sizeof(uint2), idx->stream));
     }
     idx->sq_ready = 1;
+    sq8_mark(idx, 0, idx->hiwater);  // every code is rewritten: the signed plane follows at the next search
     if (idx->hiwater > 0) {
         k_sq_encode<0><<<(unsigned)((idx->hiwater + 3) / 4), 256, 0, idx->stream>>>(
             idx->X, idx->dpad, idx->hiwater, idx->dims, nullptr, idx->sq_Dq, a, b, idx->sq_codes, idx->sq_meta);
@@ -1987,11 +2002,7 @@ static bool rq8_route(const wv_index* idx, int R) {
            idx->hiwater > 0;
 }
 
-// query chunks of rq8_candidates: key rows of at most 4 GiB
-static int64_t rq8_chunk(const wv_index* idx) {
-    const int64_t nblk = (idx->hiwater + 31) / 32;
-    return std::max<int64_t>(256, ((4ll << 30) / (nblk * 4)) / 256 * 256);
-}
+// (query chunks: rq8_chunk, rt_index.h)
 // every query's keys of a batch of nq stay in qsKey (rq8_replay_list reads them)
 static bool rq8_one_chunk(const wv_index* idx, int64_t nq) { return round_up(nq, 256) <= rq8_chunk(idx); }
 

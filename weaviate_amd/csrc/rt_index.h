@@ -248,6 +248,14 @@ struct wv_index {
     uint4* sq_codes = nullptr;    // rq-8 layout, Dq = round_up(d, 16) bytes per row
     uint2* sq_meta = nullptr;     // [cap] {sum, sum2} of the codes
     DBuf sqq, sqm;                // query codes / meta
+    // SQ block minima on the integer matrix cores (sq_mfma.hip):
+    // the signed plane x' = x - 128 of the codes (32-row tiles, rows padded to 64
+    // columns), built at the route's first use and rebuilt over the dirty slot
+    // range [sq8_lo, sq8_hi) written since the last search
+    int sq_keys = -1;             // option sq_keys: 1 wherever eligible, 0 never, -1 auto (sq8_auto)
+    unsigned char* sq8_X = nullptr;
+    int64_t sq8_cap = 0, sq8_lo = 0, sq8_hi = 0;
+    DBuf sq8Fq, sq8Fm;            // the flagged queries' codes / meta as a compact group
     // hnsw.flatSearch parameters (wv_index_hnsw_flat_search)
     int hnsw_ef = -1, ef_min = 100, ef_max = 500, ef_factor = 8, hnsw_rescore = 1;
     // the list-order hnsw flat search (search_hnsw_lists)
@@ -371,6 +379,18 @@ static inline void pq8_mark(wv_index* idx, int64_t lo, int64_t hi) {
     if (idx->pq8_hi <= idx->pq8_lo) { idx->pq8_lo = lo; idx->pq8_hi = hi; return; }
     idx->pq8_lo = std::min(idx->pq8_lo, lo);
     idx->pq8_hi = std::max(idx->pq8_hi, hi);
+}
+// SQ codes of slots [lo, hi) were (re)written: the signed plane of their blocks is stale
+static inline void sq8_mark(wv_index* idx, int64_t lo, int64_t hi) {
+    if (hi <= lo) return;
+    if (idx->sq8_hi <= idx->sq8_lo) { idx->sq8_lo = lo; idx->sq8_hi = hi; return; }
+    idx->sq8_lo = std::min(idx->sq8_lo, lo);
+    idx->sq8_hi = std::max(idx->sq8_hi, hi);
+}
+// query chunks of rq8_candidates / sq8_candidates: key rows of at most 4 GiB
+static inline int64_t rq8_chunk(const wv_index* idx) {
+    const int64_t nblk = (idx->hiwater + 31) / 32;
+    return std::max<int64_t>(256, ((4ll << 30) / (nblk * 4)) / 256 * 256);
 }
 static void invalidate_batch(wv_index* idx) {
     idx->qs_keys_nq = 0;
@@ -505,6 +525,10 @@ int search_rq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int
               uint64_t* o_ids, float* o_d, int32_t* o_n);
 int search_pq(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k, const uint32_t* valid,
               uint64_t* o_ids, float* o_d, int32_t* o_n);
+// sq_mfma.hip: the SQ arm of search_hnsw on the integer matrix cores
+bool sq8_route(const wv_index* idx, int R, int64_t nq);
+int sq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const uint32_t* valid);
+int sq8_gather(wv_index* idx, hipStream_t s, const int32_t* list, int64_t nf);
 int search_hnsw_flat(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k,
                      const uint32_t* valid, uint64_t* o_ids, float* o_d, int32_t* o_n);
 int search_hnsw_lists(wv_index* idx, hipStream_t s, const float* d_qraw, int64_t nq, int64_t qd, int k,

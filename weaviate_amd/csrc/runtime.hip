@@ -182,6 +182,7 @@ extern "C" void wv_index_destroy(wv_index* idx) {
     if (idx->sq_meta) hipFree(idx->sq_meta);
     idx->sqq.release();
     idx->sqm.release();
+    if (idx->sq8_X) hipFree(idx->sq8_X);
     if (idx->pq8_X8) hipFree(idx->pq8_X8);
     if (idx->pq8_sb) hipFree(idx->pq8_sb);
     if (idx->pq8_n2) hipFree(idx->pq8_n2);
@@ -378,6 +379,11 @@ static int ensure_capacity(wv_index* idx, int64_t need) {
         idx->pq8_X8 = nullptr; idx->pq8_sb = nullptr; idx->pq8_n2 = nullptr;
         idx->pq8_cap = 0;
     }
+    if (idx->sq8_X) {  // the signed SQ plane as well
+        hipFree(idx->sq8_X);
+        idx->sq8_X = nullptr;
+        idx->sq8_cap = 0;
+    }
     return WV_OK;
 }
 
@@ -490,6 +496,10 @@ static int requant_blocks(wv_index* idx, const uint32_t* h_slots, int64_t n) {
     if (idx->compression == WV_COMPRESSION_PQ && idx->pq_trained && n > 0) {
         const auto mm = std::minmax_element(h_slots, h_slots + n);
         pq8_mark(idx, (int64_t)*mm.first, (int64_t)*mm.second + 1);
+    }
+    if (idx->sq_ready && n > 0) {
+        const auto mm = std::minmax_element(h_slots, h_slots + n);
+        sq8_mark(idx, (int64_t)*mm.first, (int64_t)*mm.second + 1);
     }
     if (!idx->q8_planes || n <= 0) return WV_OK;
     std::vector<uint32_t> blk((size_t)n);
@@ -752,6 +762,10 @@ extern "C" int wv_index_set_option(wv_index* idx, const char* key, int64_t value
     else if (k == "q8_prio") idx->q8_prio = value ? 1 : 0;
     else if (k == "sel_split_max") idx->sel_split_max = value;
     else if (k == "rq_mfma") idx->rq_mfma = value ? 1 : 0;
+    else if (k == "sq_keys") {  // SQ block minima on the integer MFMA (d <= 1024): 1 wherever eligible, 0 never, -1 auto
+        if (value < -1 || value > 1) return set_err(WV_ERR_INVALID, "sq_keys must be -1, 0 or 1");
+        idx->sq_keys = (int)value;
+    }
     else if (k == "rq_wide") {  // rq-8 / rq-1 above 1024 rotated dims on the integer MFMA: 1 always (<= 4096), 0 never, -1 auto
         if (value < -1 || value > 1) return set_err(WV_ERR_INVALID, "rq_wide must be -1, 0 or 1");
         idx->rq_wide = (int)value;
