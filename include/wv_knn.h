@@ -631,7 +631,83 @@ typedef struct wv_stats {
 #define WV_ROUTE_LIST_SCAN 12 /* hnsw flat search in list order: k_list_dist + k_list_heap over the allow lists' entries */
 #define WV_ROUTE_BQ_PACKED 13 /* BQ block minima: k_bq_packmin (integer MFMA over the packed codes, <= 64 words) */
 #define WV_ROUTE_SQ_INT8 14   /* hnsw flat search over SQ: k_sq_keys (exact SQ block minima on the integer MFMA, d <= 1024) */
+#define WV_ROUTE_MV_MAXSIM 15 /* multi-vector flat search: k_mv_maxsim / k_mv_simple + k_list_heap (wv_mv_stats.last_route) */
 int wv_index_stats(wv_index *idx, wv_stats *out);
+
+/* ---- multi-vector (late-interaction) documents: hnsw.flatMultiSearch -------
+ * A document is a list of vectors of one dimension (ColBERT / ColPali style);
+ * a query is a list of vectors too.  hnsw.flatMultiSearch
+ * (hnsw/flat_search.go:143-212) is the filtered brute force a multi-vector
+ * collection runs when its allow list is below flatSearchCutoff
+ * (hnsw/search.go:94-129).  The score of a document is computeScore
+ * (search.go:954-1006): the sum, over the query's vectors in order, of the
+ * minimum over the document's vectors of -dot(q, t) -- one fp32 accumulator,
+ * the minimum by `dist < maxSim` from MaxFloat32 (a NaN distance is never
+ * taken), the dot product in the provider's SIMD order (wv_mv_config.variant).
+ * The pair distance is always -dot (multiDistancerProvider, hnsw/index.go:
+ * 405-406): the index's distance only decides the normalisation -- cosine-dot
+ * normalises stored vectors (insert.go:363) and query vectors (normalizeVecs,
+ * index.go:911-920), dot and l2-squared do not, so an l2-squared multi-vector
+ * index scores with -dot as well.  hamming and manhattan: WV_ERR_UNSUPPORTED
+ * at create.  Not served: compressed multi-vector storage,
+ * MUVERA, compaction of deleted documents' rows, sharding over wv_multi. */
+typedef struct wv_mv wv_mv;
+typedef struct wv_mv_config {
+    int32_t metric;          /* WV_METRIC_L2_SQUARED / _DOT / _COSINE_DOT             */
+    int32_t dims;            /* 0 = fixed by the first add (trackDimensionsOnce)      */
+    int32_t device;          /* HIP device ordinal (opened by the first add / search) */
+    int32_t variant;         /* WV_VARIANT_*                                          */
+    uint64_t id_base;        /* first doc id of this shard: slot = id - id_base       */
+} wv_mv_config;
+typedef struct wv_mv_stats {
+    uint64_t queries;
+    uint64_t batches;
+    uint64_t last_route;      /* WV_ROUTE_MV_MAXSIM after a search                    */
+    uint64_t last_scan_rows;  /* (query, listed document) pairs of the last search    */
+    uint64_t last_token_rows; /* token rows of the stored documents among them        */
+    uint64_t documents;       /* stored documents                                     */
+    uint64_t token_rows;      /* rows of the token matrix in use (deleted included)   */
+    uint64_t dims;
+    double last_kernel_ms;    /* option "timing": score + heap kernels of the last search */
+} wv_mv_stats;
+int wv_mv_create(const wv_mv_config *cfg, wv_mv **out);
+void wv_mv_destroy(wv_mv *m);
+/* hnsw.AddMultiBatch (insert.go:219-277): document i is the vectors (rows of d
+ * floats) vecs[vec_offsets[i] .. vec_offsets[i+1]); vec_offsets has n+1
+ * entries.  Errors (WV_ERR_INSERT): "addMultiBatch called with empty lists";
+ * "new node has a multi vector with length .. at position ..  Existing nodes
+ * have vectors with length .." (ValidateMultiBeforeInsert, :63-98); a document
+ * without vectors; a doc id that is already stored (the reference appends to
+ * docIDVectors[docID]; the shard deletes before it re-adds). */
+int wv_mv_add_batch(wv_mv *m, const uint64_t *doc_ids, const int64_t *vec_offsets, const float *vecs, int64_t n,
+                    int64_t d);
+/* hnsw.DeleteMulti (delete.go:105-135); ids that are not stored are ignored */
+int wv_mv_delete(wv_mv *m, const uint64_t *ids, int64_t n);
+/* hnsw.ContainsDoc, multi-vector arm (index.go:767-773): 1 / 0 */
+int wv_mv_contains_doc(wv_mv *m, uint64_t id);
+/* hnsw.flatMultiSearch for nq queries, each under its own allow list.  Query q
+ * is the vectors qvecs[q_offsets[q] .. q_offsets[q+1]) (at least one), its list
+ * allow_ids[allow_offsets[q] .. allow_offsets[q+1]) when allow_modes[q] == 1
+ * (may be empty -> no results); allow_modes[q] == 0 (or allow_modes NULL): every
+ * stored document in id order.  Lists may be unsorted and hold duplicates; ids
+ * that are not stored are skipped (the reference scores a listed id it has no
+ * vectors for with MaxFloat32 per query vector: DESIGN.md 3.13).  The heap is
+ * addResult with limit k over one worker in ascending id order (the
+ * reference's tie order is nondeterministic above flatSearchConcurrency 1); no
+ * rescoring, no ef.  Outputs [nq][k] ascending + counts; row q equals, bit for
+ * bit, the one-query call.  Options (wv_mv_set_option): "mv_tile" (-1 auto, 0
+ * k_mv_simple, 1 k_mv_maxsim), "mv_list_rows" (entries per launch group, 0 =
+ * default), "timing". */
+int wv_mv_search_batch(wv_mv *m, const float *qvecs, const int64_t *q_offsets, int64_t nq, int64_t d, int32_t k,
+                       const uint64_t *allow_ids, const int64_t *allow_offsets, const int32_t *allow_modes,
+                       uint64_t *out_ids, float *out_dists, int32_t *out_counts);
+/* hnsw.QueryMultiVectorDistancer(query).DistanceFunc(id) for n ids
+ * (search.go:1033-1045); an id that is not stored: "docID .. is not in the
+ * vector index" */
+int wv_mv_query_distances(wv_mv *m, const float *qvecs, int64_t nqv, int64_t d, const uint64_t *ids, int64_t n,
+                          float *out);
+int wv_mv_set_option(wv_mv *m, const char *key, int64_t value);
+int wv_mv_get_stats(wv_mv *m, wv_mv_stats *out);
 
 /* Diagnostic hook (tests): the last MFMA batch's candidates [nq][KP]:
  * approximate distances A, exact distances E, slots I (0xFFFFFFFF = none), and

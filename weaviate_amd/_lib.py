@@ -92,7 +92,31 @@ class WvStats(C.Structure):
 # wv_stats.last_route (include/wv_knn.h WV_ROUTE_*)
 ROUTES = {0: "none", 1: "qs_bf16", 2: "qs_w4", 3: "qs_int8", 4: "f32_select", 5: "gemv", 6: "bq_int8", 7: "bq_valu",
           8: "pq_int8", 9: "q8_gemv", 10: "rq8_int8", 11: "l1_tile", 12: "list_scan",
-          13: "bq_packed", 14: "sq_int8"}
+          13: "bq_packed", 14: "sq_int8", 15: "mv_maxsim"}
+
+
+class WvMvConfig(C.Structure):
+    _fields_ = [
+        ("metric", C.c_int32),
+        ("dims", C.c_int32),
+        ("device", C.c_int32),
+        ("variant", C.c_int32),
+        ("id_base", C.c_uint64),
+    ]
+
+
+class WvMvStats(C.Structure):
+    _fields_ = [
+        ("queries", C.c_uint64),
+        ("batches", C.c_uint64),
+        ("last_route", C.c_uint64),
+        ("last_scan_rows", C.c_uint64),
+        ("last_token_rows", C.c_uint64),
+        ("documents", C.c_uint64),
+        ("token_rows", C.c_uint64),
+        ("dims", C.c_uint64),
+        ("last_kernel_ms", C.c_double),
+    ]
 
 
 P = C.c_void_p
@@ -201,6 +225,15 @@ SIGNATURES = {
     "wv_index_search_by_vector": (C.c_int, [P, pf32, i64, i32, pu64, i64, i32, pu64, pf32, pi32]),
     "wv_index_batcher_stats": (C.c_int, [P, C.POINTER(C.c_int64)]),
     "wv_index_load_segments": (C.c_int, [P, C.POINTER(C.c_char_p), i32, i32, C.POINTER(C.c_int64)]),
+    "wv_mv_create": (C.c_int, [C.POINTER(WvMvConfig), C.POINTER(P)]),
+    "wv_mv_destroy": (None, [P]),
+    "wv_mv_add_batch": (C.c_int, [P, pu64, P, pf32, i64, i64]),
+    "wv_mv_delete": (C.c_int, [P, pu64, i64]),
+    "wv_mv_contains_doc": (C.c_int, [P, u64]),
+    "wv_mv_search_batch": (C.c_int, [P, pf32, P, i64, i64, i32, pu64, P, pi32, pu64, pf32, pi32]),
+    "wv_mv_query_distances": (C.c_int, [P, pf32, i64, i64, pu64, i64, pf32]),
+    "wv_mv_set_option": (C.c_int, [P, C.c_char_p, i64]),
+    "wv_mv_get_stats": (C.c_int, [P, C.POINTER(WvMvStats)]),
 }
 
 _lib = None
