@@ -632,6 +632,7 @@ typedef struct wv_stats {
 #define WV_ROUTE_BQ_PACKED 13 /* BQ block minima: k_bq_packmin (integer MFMA over the packed codes, <= 64 words) */
 #define WV_ROUTE_SQ_INT8 14   /* hnsw flat search over SQ: k_sq_keys (exact SQ block minima on the integer MFMA, d <= 1024) */
 #define WV_ROUTE_MV_MAXSIM 15 /* multi-vector flat search: k_mv_maxsim / k_mv_simple + k_list_heap (wv_mv_stats.last_route) */
+#define WV_ROUTE_MV_KEYS 16   /* ... with k_mv_keys + k_mv_cut first (bf16 matrix-core MaxSim keys), the exact kernel on the survivors */
 int wv_index_stats(wv_index *idx, wv_stats *out);
 
 /* ---- multi-vector (late-interaction) documents: hnsw.flatMultiSearch -------
@@ -662,13 +663,18 @@ typedef struct wv_mv_config {
 typedef struct wv_mv_stats {
     uint64_t queries;
     uint64_t batches;
-    uint64_t last_route;      /* WV_ROUTE_MV_MAXSIM after a search                    */
+    uint64_t last_route;      /* WV_ROUTE_MV_KEYS when any query took keys, else WV_ROUTE_MV_MAXSIM */
     uint64_t last_scan_rows;  /* (query, listed document) pairs of the last search    */
     uint64_t last_token_rows; /* token rows of the stored documents among them        */
     uint64_t documents;       /* stored documents                                     */
     uint64_t token_rows;      /* rows of the token matrix in use (deleted included)   */
     uint64_t dims;
     double last_kernel_ms;    /* option "timing": score + heap kernels of the last search */
+    uint64_t last_key_queries;      /* queries of the last search that took the key route          */
+    uint64_t last_candidates;       /* candidates the cut handed to the exact kernel, all queries  */
+    uint64_t last_fallback_queries; /* key queries answered over their whole list after all: ties, */
+                                    /* candidate overflow, the norm guard, non-finite keys          */
+    double last_key_ms;             /* option "timing": k_mv_qprep + k_mv_keys + k_mv_cut          */
 } wv_mv_stats;
 int wv_mv_create(const wv_mv_config *cfg, wv_mv **out);
 void wv_mv_destroy(wv_mv *m);
@@ -697,7 +703,19 @@ int wv_mv_contains_doc(wv_mv *m, uint64_t id);
  * rescoring, no ef.  Outputs [nq][k] ascending + counts; row q equals, bit for
  * bit, the one-query call.  Options (wv_mv_set_option): "mv_tile" (-1 auto, 0
  * k_mv_simple, 1 k_mv_maxsim), "mv_list_rows" (entries per launch group, 0 =
- * default), "timing". */
+ * default), "timing".
+ * The key route (WV_ROUTE_MV_KEYS): a query whose list holds
+ * at least "mv_keys_min" ids (default 4096; every stored document counts for a
+ * query without a list) first gets a bf16 matrix-core MaxSim key with a proven
+ * error bound per listed document; the documents that can be among the k + 1
+ * best (at most "mv_keys_cap" of them, default max(1024, 8 (k + 1))) go through
+ * the exact kernel and the heap with limit k + 1.  When those k + 1 scores are
+ * pairwise distinct the first k are the answer; else -- and for a query whose
+ * norms leave [2^-60, 2^60], whose keys are not finite or whose candidates
+ * overflow -- the query is answered over its whole list as before.  Results
+ * are the same bit for bit.  "mv_keys": -1 auto (the default), 0 never, 1
+ * wherever eligible (dims <= 1024, k + 1 within the heap limit, <= 65536
+ * vectors per query).  Queries of one batch split between the routes. */
 int wv_mv_search_batch(wv_mv *m, const float *qvecs, const int64_t *q_offsets, int64_t nq, int64_t d, int32_t k,
                        const uint64_t *allow_ids, const int64_t *allow_offsets, const int32_t *allow_modes,
                        uint64_t *out_ids, float *out_dists, int32_t *out_counts);
@@ -708,6 +726,12 @@ int wv_mv_query_distances(wv_mv *m, const float *qvecs, int64_t nqv, int64_t d, 
                           float *out);
 int wv_mv_set_option(wv_mv *m, const char *key, int64_t value);
 int wv_mv_get_stats(wv_mv *m, wv_mv_stats *out);
+/* Diagnostic hook (tests) of the key route: batch row q of the last search that
+ * took keys: for every entry of its planned list (ascending distinct slots) the
+ * key, its error bound eps and the slot (doc id - id_base); a listed slot
+ * without a document has key +inf and eps 0.  Call with keys == NULL to read *n
+ * only. */
+int wv_mv_debug_keys(wv_mv *m, int64_t q, float *keys, float *eps, uint32_t *slots, int64_t *n);
 
 /* Diagnostic hook (tests): the last MFMA batch's candidates [nq][KP]:
  * approximate distances A, exact distances E, slots I (0xFFFFFFFF = none), and

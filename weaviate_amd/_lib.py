@@ -92,7 +92,7 @@ class WvStats(C.Structure):
 # wv_stats.last_route (include/wv_knn.h WV_ROUTE_*)
 ROUTES = {0: "none", 1: "qs_bf16", 2: "qs_w4", 3: "qs_int8", 4: "f32_select", 5: "gemv", 6: "bq_int8", 7: "bq_valu",
           8: "pq_int8", 9: "q8_gemv", 10: "rq8_int8", 11: "l1_tile", 12: "list_scan",
-          13: "bq_packed", 14: "sq_int8", 15: "mv_maxsim"}
+          13: "bq_packed", 14: "sq_int8", 15: "mv_maxsim", 16: "mv_keys"}
 
 
 class WvMvConfig(C.Structure):
@@ -116,6 +116,10 @@ class WvMvStats(C.Structure):
         ("token_rows", C.c_uint64),
         ("dims", C.c_uint64),
         ("last_kernel_ms", C.c_double),
+        ("last_key_queries", C.c_uint64),
+        ("last_candidates", C.c_uint64),
+        ("last_fallback_queries", C.c_uint64),
+        ("last_key_ms", C.c_double),
     ]
 
 
@@ -234,6 +238,7 @@ SIGNATURES = {
     "wv_mv_query_distances": (C.c_int, [P, pf32, i64, i64, pu64, i64, pf32]),
     "wv_mv_set_option": (C.c_int, [P, C.c_char_p, i64]),
     "wv_mv_get_stats": (C.c_int, [P, C.POINTER(WvMvStats)]),
+    "wv_mv_debug_keys": (C.c_int, [P, i64, pf32, pf32, C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -21,7 +21,7 @@ NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # rq8_wide.hip: the same flag; its epilogue (rq8_block_min) is float code, element-wise scalar ops there.
 UNIT_FLAGS = {"bq_packed.hip": NO_PK_F32, "rq8_wide.hip": NO_PK_F32}
 SOURCES = [os.path.join(HERE, "csrc", f) for f in (
-    "runtime.hip", "qs_runtime.hip", "qs_exact.hip", "qs_replay.hip", "quant_runtime.hip", "multi.hip", "bq_packed.hip", "rq8_wide.hip", "sq_mfma.hip", "mv_runtime.hip", "mv_kernels.hip", "rt_index.h", "kernels.hip", "bq_kernels.hip",
+    "runtime.hip", "qs_runtime.hip", "qs_exact.hip", "qs_replay.hip", "quant_runtime.hip", "multi.hip", "bq_packed.hip", "rq8_wide.hip", "sq_mfma.hip", "mv_runtime.hip", "mv_kernels.hip", "mv_keys.hip", "rt_index.h", "kernels.hip", "bq_kernels.hip",
     "pq_kernels.hip", "kernels_bf3.hip", "rq_kernels.hip", "lsm_segment.hip", "batcher.hip", "gemv_kernels.hip",
     "qs_kernels.hip", "q8_kernels.hip", "sq_kernels.hip", "vector_index.hip", "wv_device.h", "rq8_mfma.hip", "batch_row.h", "key_plan.h", "l1_kernels.hip", "list_plan.h", "list_kernels.hip", "pqa_plan.h", "dyn_lds.h")] + [os.path.join(REPO, "include", "wv_knn.h")]
 OBJDIR = os.path.join(HERE, "build")

@@ -19,8 +19,18 @@
 // per group k_mv_maxsim / k_mv_simple (mv_kernels.hip) writes the score of every
 // (query, listed document) and k_list_heap (list_kernels.hip, unchanged) runs
 // the reference's heap with limit k over them in ascending id order.
+//
+// The key route (mv_keys.hip, DESIGN.md §3.13b, WV_ROUTE_MV_KEYS): queries whose
+// lists hold at least mv_keys_min ids first take k_mv_keys over bf16 planes
+//   Th, Tl   [tok_cap][dpad] bf16  T = Th + Tl + r, built lazily over the rows
+//                                  added since the last key search
+//   tnorm    [tok_cap] fp32        row norms;  tmax [slot]: a document's largest
+// and k_mv_cut; the candidates then go through the search above with limit
+// k + 1, and a query whose k + 1 scores are not pairwise distinct -- or that the
+// key pass flagged -- is answered by the search above over its original list.
 #include "rt_index.h"
 #include "mv_kernels.hip"
+#include "mv_keys.hip"
 
 #include <unordered_set>
 
@@ -32,6 +42,11 @@ constexpr int MV_QT = 4, MV_RT = 2;
 constexpr int MV_QT5 = 2, MV_RT5 = 2;
 constexpr size_t MV_LDS_TILE = 32 * 1024;  // the query is staged whole while it fits
 constexpr size_t MV_LDS_MAX = 64 * 1024;   // QT rows must fit, else the simple arm
+
+// the key route's auto rule and its smallest list, from the crossover measured in DESIGN.md §3.13b
+constexpr bool MV_KEYS_AUTO = true;
+constexpr int64_t MV_KEYS_MIN = 4096;
+constexpr size_t MVK_LDS_TILE = 60 * 1024;  // the query tile's hi / lo rows while more than 32 vectors fit
 
 }  // namespace
 
@@ -54,6 +69,23 @@ struct wv_mv {
     int64_t mv_list_rows = 0;   // option mv_list_rows: entries per launch group (0: 4 Mi)
     int timing = 0;             // option timing: events around the score and heap kernels
     DBuf stage, Q, qspan, dDocs, dPresent, pool, lq, pieces, Ec, Bc, Ab, oI, oD, oN;
+    // the key route (mv_keys.hip): nothing below is allocated before its first search
+    int mv_keys = -1;           // option mv_keys: -1 auto (MV_KEYS_AUTO), 0 never, 1 wherever eligible
+    int64_t mv_keys_min = -1;   // option mv_keys_min: listed ids from which a query takes keys (-1: MV_KEYS_MIN)
+    int64_t mv_keys_cap = 0;    // option mv_keys_cap: candidate slots per query (0: max(1024, 8 (k + 1)))
+    uint16_t *Th = nullptr, *Tl = nullptr;
+    float* tnorm = nullptr;
+    int64_t plane_cap = 0, built = 0;  // rows allocated / converted
+    bool tmax_valid = false;           // tmax covers every stored document
+    hipEvent_t evk0 = nullptr, evk1 = nullptr;
+    DBuf tmax, Kc, kAb, cS, kflags, cand, ccnt;
+    // the last key search (wv_mv_debug_keys): its plan, every listed query's first entry in Kc / kAb,
+    // the queries' c sum |q| and flags
+    ListPlan kplan;
+    std::vector<int64_t> kabs;
+    std::vector<float> h_cS;
+    std::vector<int32_t> h_kflags;
+    bool kdbg = false;
     wv_mv_stats stats{};
 };
 
@@ -69,10 +101,46 @@ int mv_device(wv_mv* m) {
     return WV_OK;
 }
 
+// the bf16 planes and row norms with room for `cap` rows; the converted rows move with them
+int mv_alloc_planes(wv_mv* m, int64_t cap) {
+    if (cap <= m->plane_cap) return WV_OK;
+    uint16_t *nh = nullptr, *nl = nullptr;
+    float* nn = nullptr;
+    const size_t pb = (size_t)cap * m->dpad * sizeof(uint16_t), ob = (size_t)m->built * m->dpad * sizeof(uint16_t);
+    hipError_t e = hipMalloc(&nh, pb);
+    if (e == hipSuccess) e = hipMalloc(&nl, pb);
+    if (e == hipSuccess) e = hipMalloc(&nn, (size_t)cap * sizeof(float));
+    if (e == hipSuccess && m->built > 0) {
+        e = hipMemcpyAsync(nh, m->Th, ob, hipMemcpyDeviceToDevice, m->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(nl, m->Tl, ob, hipMemcpyDeviceToDevice, m->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(nn, m->tnorm, (size_t)m->built * sizeof(float), hipMemcpyDeviceToDevice, m->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    if (e != hipSuccess) {
+        if (nh) hipFree(nh);
+        if (nl) hipFree(nl);
+        if (nn) hipFree(nn);
+        return set_err(WV_ERR_HIP, "token planes: %s", hipGetErrorString(e));
+    }
+    if (m->Th) hipFree(m->Th);
+    if (m->Tl) hipFree(m->Tl);
+    if (m->tnorm) hipFree(m->tnorm);
+    m->Th = nh;
+    m->Tl = nl;
+    m->tnorm = nn;
+    m->plane_cap = cap;
+    return WV_OK;
+}
+
 // room for `rows` token rows; the rows already stored move with the buffer
 int mv_ensure_tokens(wv_mv* m, int64_t rows) {
     if (rows <= m->tok_cap) return WV_OK;
     const int64_t cap = std::max<int64_t>(std::max<int64_t>(rows, m->tok_cap * 2), 1024);
+    if (m->Th) {  // the planes grow with T once they exist
+        const int rc = mv_alloc_planes(m, cap);
+        if (rc) return rc;
+    }
     float* nt = nullptr;
     HIPCHK(hipMalloc(&nt, (size_t)cap * m->dpad * sizeof(float)));
     hipError_t e = hipSuccess;
@@ -205,6 +273,208 @@ int mv_upload_queries(wv_mv* m, const float* qvecs, const int64_t* q_offsets, in
     return WV_OK;
 }
 
+// the exact search of the queries with lo[q] >= 0 over their lists ids[lo[q] .. hi[q]) (the uploaded
+// queries and records): per launch group the score kernel and the heap with `limit`.  Rows [nq][limit]
+// and counts [nq] of those queries into the host arrays; the other queries' rows are not defined.
+int mv_exact_search(wv_mv* m, const uint64_t* ids, const int64_t* lo, const int64_t* hi, int64_t nq, int limit,
+                    int64_t max_qv, bool count_rows, uint64_t* out_ids, float* out_dists, int32_t* out_counts) {
+    hipStream_t s = m->stream;
+    const int64_t budget = m->mv_list_rows > 0 ? m->mv_list_rows : (int64_t)4 << 20;
+    const ListPlan plan = list_plan(ids, lo, hi, nq, m->id_base, m->hiwater, budget, 1);
+    if (count_rows) {
+        m->stats.last_scan_rows += (uint64_t)plan.scanned;
+        for (const ListQuery& q : plan.queries)
+            for (int64_t i = 0; i < q.len; i++) {
+                const uint32_t sl = plan.pool[(size_t)(q.pool_begin + i)];
+                if (mv_present(m, sl)) m->stats.last_token_rows += (uint64_t)m->h_docs[sl].len;
+            }
+    }
+    int rc = mv_upload_plan(m, plan.pool, plan.queries, plan.pieces, plan.max_entries);
+    if (rc) return rc;
+    HIPCHK(m->oI.ensure((size_t)nq * limit * sizeof(uint64_t)));
+    HIPCHK(m->oD.ensure((size_t)nq * limit * sizeof(float)));
+    HIPCHK(m->oN.ensure((size_t)nq * sizeof(int32_t)));
+    const size_t lds_h = replay_scan_lds(limit);
+    const bool pk = limit <= PACKED_REPLAY_MAX_K;
+    HIPCHK(set_dyn_lds(pk ? (const void*)k_list_heap<true> : (const void*)k_list_heap<false>, lds_h));
+    if (m->timing && !m->ev0) {
+        HIPCHK(hipEventCreate(&m->ev0));
+        HIPCHK(hipEventCreate(&m->ev1));
+    }
+    if (m->timing) HIPCHK(hipEventRecord(m->ev0, s));
+    MvArgs a = mv_args(m);
+    for (const ListGroup& gr : plan.groups) {
+        a.pieces = m->pieces.as<ListPiece>() + gr.piece0;
+        rc = mv_launch_scores(m, s, a, (unsigned)(gr.piece1 - gr.piece0), max_qv);
+        if (rc) return rc;
+        const unsigned nl = (unsigned)(gr.lq1 - gr.lq0);
+        if (pk)
+            k_list_heap<true><<<nl, 64, lds_h, s>>>(a.Ec, a.Bc, a.Ab, a.pool, a.lq + gr.lq0, (int)nl, limit, m->id_base,
+                                                    m->oI.as<uint64_t>(), m->oD.as<float>(), m->oN.as<int32_t>());
+        else
+            k_list_heap<false><<<nl, 64, lds_h, s>>>(a.Ec, a.Bc, a.Ab, a.pool, a.lq + gr.lq0, (int)nl, limit, m->id_base,
+                                                     m->oI.as<uint64_t>(), m->oD.as<float>(), m->oN.as<int32_t>());
+        HIPCHK(hipGetLastError());
+    }
+    if (m->timing) HIPCHK(hipEventRecord(m->ev1, s));
+    HIPCHK(hipMemcpyAsync(out_ids, m->oI.p, (size_t)nq * limit * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_dists, m->oD.p, (size_t)nq * limit * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_counts, m->oN.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (m->timing) {
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, m->ev0, m->ev1);
+        m->stats.last_kernel_ms += ms;
+    }
+    return WV_OK;
+}
+
+// the planes of the rows added since the last key search, and every document's largest row norm
+int mv_build_planes(wv_mv* m) {
+    hipStream_t s = m->stream;
+    int rc = mv_alloc_planes(m, m->tok_cap);
+    if (rc) return rc;
+    if (m->built < m->tok_used) {
+        const int64_t rows = m->tok_used - m->built;
+        k_mv_planes<<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(m->T, m->built, m->tok_used, m->dims, m->dpad, m->Th, m->Tl,
+                                                               m->tnorm);
+        HIPCHK(hipGetLastError());
+        m->built = m->tok_used;
+    }
+    if (!m->tmax_valid) {
+        HIPCHK(m->tmax.ensure((size_t)m->hiwater * sizeof(float)));
+        k_mv_tmax<<<(unsigned)((m->hiwater + 255) / 256), 256, 0, s>>>(m->dDocs.as<MvSpan>(), m->hiwater, m->tnorm,
+                                                                       m->tmax.as<float>());
+        HIPCHK(hipGetLastError());
+        m->tmax_valid = true;
+    }
+    return WV_OK;
+}
+
+int mv_launch_keys(hipStream_t s, const MvKeyArgs& a, unsigned np) {
+    if (np == 0) return WV_OK;
+    const size_t lds = mvk_lds_bytes(a.qtile, a.dpad);
+    const void* fn = a.dpad == 32 ? (const void*)k_mv_keys<2> : a.dpad == 64 ? (const void*)k_mv_keys<4>
+                   : a.dpad == 96 ? (const void*)k_mv_keys<6> : a.dpad == 128 ? (const void*)k_mv_keys<8>
+                                                                              : (const void*)k_mv_keys<0>;
+    HIPCHK(set_dyn_lds(fn, lds));
+    if (a.dpad == 32) k_mv_keys<2><<<np, 256, lds, s>>>(a);
+    else if (a.dpad == 64) k_mv_keys<4><<<np, 256, lds, s>>>(a);
+    else if (a.dpad == 96) k_mv_keys<6><<<np, 256, lds, s>>>(a);
+    else if (a.dpad == 128) k_mv_keys<8><<<np, 256, lds, s>>>(a);
+    else k_mv_keys<0><<<np, 256, lds, s>>>(a);
+    HIPCHK(hipGetLastError());
+    return WV_OK;
+}
+
+// the key pass of the queries with lo[q] >= 0: keys, cut, one download.  cand[q]: the candidate slots of a
+// query the pass did not flag (ascending); flagged[q]: MVK_FLAG_* of one it did.
+int mv_key_pass(wv_mv* m, const uint64_t* ids, const int64_t* lo, const int64_t* hi, int64_t nq, int k,
+                int64_t max_qv, std::vector<std::vector<uint32_t>>& cand, std::vector<int32_t>& flagged) {
+    hipStream_t s = m->stream;
+    int rc = mv_build_planes(m);
+    if (rc) return rc;
+    const int64_t budget = m->mv_list_rows > 0 ? m->mv_list_rows : (int64_t)4 << 20;
+    m->kdbg = false;
+    m->kplan = list_plan(ids, lo, hi, nq, m->id_base, m->hiwater, budget, 1);
+    const ListPlan& plan = m->kplan;
+    int64_t total = 0, longest = 1;
+    std::vector<int64_t> gbase;
+    for (const ListGroup& gr : plan.groups) {
+        gbase.push_back(total);
+        total += gr.entries;
+    }
+    m->kabs.assign(plan.queries.size(), 0);
+    for (size_t g = 0; g < plan.groups.size(); g++)
+        for (int64_t i = plan.groups[g].lq0; i < plan.groups[g].lq1; i++) {
+            const ListQuery& q = plan.queries[(size_t)i];
+            m->kabs[(size_t)i] = gbase[g] + q.e_begin;
+            longest = std::max(longest, q.len);
+        }
+    const int64_t want = m->mv_keys_cap > 0 ? m->mv_keys_cap : std::max<int64_t>(1024, 8 * ((int64_t)k + 1));
+    const int cap = (int)std::min<int64_t>(want, longest);
+    HIPCHK(m->pool.ensure(plan.pool.size() * sizeof(uint32_t)));
+    HIPCHK(m->lq.ensure(plan.queries.size() * sizeof(ListQuery)));
+    HIPCHK(m->pieces.ensure(plan.pieces.size() * sizeof(ListPiece)));
+    if (!plan.pool.empty())
+        HIPCHK(hipMemcpyAsync(m->pool.p, plan.pool.data(), plan.pool.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (!plan.queries.empty())
+        HIPCHK(hipMemcpyAsync(m->lq.p, plan.queries.data(), plan.queries.size() * sizeof(ListQuery), hipMemcpyHostToDevice, s));
+    if (!plan.pieces.empty())
+        HIPCHK(hipMemcpyAsync(m->pieces.p, plan.pieces.data(), plan.pieces.size() * sizeof(ListPiece), hipMemcpyHostToDevice, s));
+    const int64_t me = std::max<int64_t>(total, LIST_CHUNK);
+    HIPCHK(m->Kc.ensure((size_t)me * sizeof(float)));
+    HIPCHK(m->kAb.ensure((size_t)(me / 64) * sizeof(uint64_t)));
+    HIPCHK(m->cS.ensure((size_t)nq * sizeof(float)));
+    HIPCHK(m->kflags.ensure((size_t)nq * sizeof(int32_t)));
+    HIPCHK(m->cand.ensure((size_t)nq * cap * sizeof(uint32_t)));
+    HIPCHK(m->ccnt.ensure((size_t)nq * sizeof(int32_t)));
+    if (m->timing && !m->evk0) {
+        HIPCHK(hipEventCreate(&m->evk0));
+        HIPCHK(hipEventCreate(&m->evk1));
+    }
+    if (m->timing) HIPCHK(hipEventRecord(m->evk0, s));
+    k_mv_qprep<<<(unsigned)nq, 256, 0, s>>>(m->Q.as<float>(), m->qspan.as<MvSpan>(), m->dims, m->dpad, m->cS.as<float>(),
+                                            m->kflags.as<int32_t>());
+    HIPCHK(hipGetLastError());
+    MvKeyArgs a{};
+    a.pool = m->pool.as<uint32_t>();
+    a.lq = m->lq.as<ListQuery>();
+    a.present = m->dPresent.as<uint32_t>();
+    a.docs = m->dDocs.as<MvSpan>();
+    a.Th = m->Th;
+    a.Tl = m->Tl;
+    a.tmax = m->tmax.as<float>();
+    a.Q = m->Q.as<float>();
+    a.qspan = m->qspan.as<MvSpan>();
+    a.flags = m->kflags.as<int32_t>();
+    a.d = m->dims;
+    a.dpad = m->dpad;
+    const int64_t fit = (int64_t)(MVK_LDS_TILE / mvk_lds_bytes(1, m->dpad)) / 32 * 32;
+    a.qtile = (int)std::min<int64_t>(std::min<int64_t>(std::max<int64_t>(fit, 32), MVK_QTILE_MAX),
+                                     round_up(std::max<int64_t>(max_qv, 1), 32));
+    for (size_t g = 0; g < plan.groups.size(); g++) {
+        const ListGroup& gr = plan.groups[g];
+        a.pieces = m->pieces.as<ListPiece>() + gr.piece0;
+        a.Kc = m->Kc.as<float>() + gbase[g];
+        a.Ab = m->kAb.as<uint64_t>() + gbase[g] / 64;
+        rc = mv_launch_keys(s, a, (unsigned)(gr.piece1 - gr.piece0));
+        if (rc) return rc;
+        k_mv_cut<<<(unsigned)(gr.lq1 - gr.lq0), 256, 0, s>>>(a.Kc, a.Ab, a.pool, a.lq + gr.lq0, a.tmax, m->cS.as<float>(),
+                                                             a.flags, k + 1, cap, m->cand.as<uint32_t>(),
+                                                             m->ccnt.as<int32_t>());
+        HIPCHK(hipGetLastError());
+    }
+    if (m->timing) HIPCHK(hipEventRecord(m->evk1, s));
+    std::vector<int32_t> cnt((size_t)nq);
+    std::vector<uint32_t> slots((size_t)nq * cap);
+    m->h_cS.resize((size_t)nq);
+    m->h_kflags.resize((size_t)nq);
+    HIPCHK(hipMemcpyAsync(cnt.data(), m->ccnt.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(m->h_kflags.data(), m->kflags.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(m->h_cS.data(), m->cS.p, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(slots.data(), m->cand.p, (size_t)nq * cap * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // the one synchronisation between the two stages
+    if (m->timing) {
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, m->evk0, m->evk1);
+        m->stats.last_key_ms = ms;
+    }
+    for (const ListQuery& q : plan.queries) {
+        const size_t r = (size_t)q.q;
+        flagged[r] = m->h_kflags[r];
+        if (flagged[r]) continue;  // its pairs are counted by the exact search of its list
+        cand[r].assign(slots.begin() + r * cap, slots.begin() + r * cap + cnt[r]);
+        m->stats.last_scan_rows += (uint64_t)q.len;
+        for (int64_t j = 0; j < q.len; j++) {
+            const uint32_t sl = plan.pool[(size_t)(q.pool_begin + j)];
+            if (mv_present(m, sl)) m->stats.last_token_rows += (uint64_t)m->h_docs[sl].len;
+        }
+    }
+    m->kdbg = true;
+    return WV_OK;
+}
+
 }  // namespace
 
 extern "C" int wv_mv_create(const wv_mv_config* cfg, wv_mv** out) {
@@ -236,8 +506,13 @@ extern "C" void wv_mv_destroy(wv_mv* m) {
         hipSetDevice(m->device);
         if (m->stream) hipStreamSynchronize(m->stream);
         if (m->T) hipFree(m->T);
+        if (m->Th) hipFree(m->Th);
+        if (m->Tl) hipFree(m->Tl);
+        if (m->tnorm) hipFree(m->tnorm);
         if (m->ev0) hipEventDestroy(m->ev0);
         if (m->ev1) hipEventDestroy(m->ev1);
+        if (m->evk0) hipEventDestroy(m->evk0);
+        if (m->evk1) hipEventDestroy(m->evk1);
         if (m->stream) hipStreamDestroy(m->stream);
     }
     delete m;
@@ -301,6 +576,8 @@ extern "C" int wv_mv_add_batch(wv_mv* m, const uint64_t* doc_ids, const int64_t*
     m->tok_used += rows;
     m->ndocs += n;
     m->meta_dirty = true;
+    m->tmax_valid = false;
+    m->kdbg = false;
     return WV_OK;
 }
 
@@ -357,7 +634,8 @@ extern "C" int wv_mv_search_batch(wv_mv* m, const float* qvecs, const int64_t* q
     m->stats.batches++;
     m->stats.last_route = WV_ROUTE_MV_MAXSIM;
     m->stats.last_scan_rows = m->stats.last_token_rows = 0;
-    m->stats.last_kernel_ms = 0.0;
+    m->stats.last_kernel_ms = m->stats.last_key_ms = 0.0;
+    m->stats.last_key_queries = m->stats.last_candidates = m->stats.last_fallback_queries = 0;
     if (m->ndocs == 0) {
         for (int64_t q = 0; q < nq; q++) out_counts[q] = 0;
         return WV_OK;
@@ -386,57 +664,91 @@ extern "C" int wv_mv_search_batch(wv_mv* m, const float* qvecs, const int64_t* q
         lo[(size_t)q] = listed ? allow_offsets[q] : n_allow;
         hi[(size_t)q] = listed ? allow_offsets[q + 1] : n_allow + m->ndocs;
     }
-    const int64_t budget = m->mv_list_rows > 0 ? m->mv_list_rows : (int64_t)4 << 20;
-    const ListPlan plan = list_plan(ids, lo.data(), hi.data(), nq, m->id_base, m->hiwater, budget, 1);
-    m->stats.last_scan_rows = (uint64_t)plan.scanned;
-    for (const ListQuery& q : plan.queries)
-        for (int64_t i = 0; i < q.len; i++) {
-            const uint32_t sl = plan.pool[(size_t)(q.pool_begin + i)];
-            if (mv_present(m, sl)) m->stats.last_token_rows += (uint64_t)m->h_docs[sl].len;
-        }
     rc = mv_device(m);
     if (rc) return rc;
-    hipStream_t s = m->stream;
     rc = mv_sync_meta(m);
     if (rc) return rc;
     rc = mv_upload_queries(m, qvecs, q_offsets, nq);
     if (rc) return rc;
-    rc = mv_upload_plan(m, plan.pool, plan.queries, plan.pieces, plan.max_entries);
+    // the queries of the key route: option mv_keys, the kernel's widths, the heap's room for k + 1, a
+    // list of at least mv_keys_min ids
+    const bool keys_on = (m->mv_keys == 1 || (m->mv_keys < 0 && MV_KEYS_AUTO)) && m->dpad <= MVK_MAX_DPAD &&
+                         max_qv <= MVK_MAX_QV && k < INT32_MAX && replay_scan_lds(k + 1) <= 160 * 1024;
+    const int64_t kmin = std::max<int64_t>(m->mv_keys_min >= 0 ? m->mv_keys_min : MV_KEYS_MIN, 1);
+    std::vector<int64_t> klo((size_t)nq, -1);
+    int64_t nkey = 0;
+    for (int64_t q = 0; q < nq && keys_on; q++)
+        if (hi[(size_t)q] - lo[(size_t)q] >= kmin) {
+            klo[(size_t)q] = lo[(size_t)q];
+            nkey++;
+        }
+    if (nkey == 0)  // today's call
+        return mv_exact_search(m, ids, lo.data(), hi.data(), nq, k, max_qv, true, out_ids, out_dists, out_counts);
+
+    m->stats.last_route = WV_ROUTE_MV_KEYS;
+    m->stats.last_key_queries = (uint64_t)nkey;
+    std::vector<std::vector<uint32_t>> cand((size_t)nq);
+    std::vector<int32_t> flagged((size_t)nq, 0);
+    rc = mv_key_pass(m, ids, klo.data(), hi.data(), nq, k, max_qv, cand, flagged);
     if (rc) return rc;
-    HIPCHK(m->oI.ensure((size_t)nq * k * sizeof(uint64_t)));
-    HIPCHK(m->oD.ensure((size_t)nq * k * sizeof(float)));
-    HIPCHK(m->oN.ensure((size_t)nq * sizeof(int32_t)));
-    const size_t lds_h = replay_scan_lds(k);
-    const bool pk = k <= PACKED_REPLAY_MAX_K;
-    HIPCHK(set_dyn_lds(pk ? (const void*)k_list_heap<true> : (const void*)k_list_heap<false>, lds_h));
-    if (m->timing && !m->ev0) {
-        HIPCHK(hipEventCreate(&m->ev0));
-        HIPCHK(hipEventCreate(&m->ev1));
+    // second stage: the candidates as each query's allow list, the exact search with limit k + 1
+    const int k1 = k + 1;
+    std::vector<uint64_t> cids;
+    std::vector<int64_t> clo((size_t)nq, -1), chi((size_t)nq, -1);
+    int64_t nsecond = 0;
+    for (int64_t q = 0; q < nq; q++) {
+        if (klo[(size_t)q] < 0 || flagged[(size_t)q]) continue;
+        clo[(size_t)q] = (int64_t)cids.size();
+        for (uint32_t sl : cand[(size_t)q]) cids.push_back(m->id_base + sl);
+        chi[(size_t)q] = (int64_t)cids.size();
+        m->stats.last_candidates += (uint64_t)cand[(size_t)q].size();
+        nsecond++;
     }
-    if (m->timing) HIPCHK(hipEventRecord(m->ev0, s));
-    MvArgs a = mv_args(m);
-    for (const ListGroup& gr : plan.groups) {
-        a.pieces = m->pieces.as<ListPiece>() + gr.piece0;
-        rc = mv_launch_scores(m, s, a, (unsigned)(gr.piece1 - gr.piece0), max_qv);
+    if (cids.empty()) cids.push_back(0);
+    std::vector<uint64_t> tI;
+    std::vector<float> tD;
+    std::vector<int32_t> tN((size_t)nq);
+    if (nsecond) {
+        tI.resize((size_t)nq * k1);
+        tD.resize((size_t)nq * k1);
+        rc = mv_exact_search(m, cids.data(), clo.data(), chi.data(), nq, k1, max_qv, false, tI.data(), tD.data(), tN.data());
         if (rc) return rc;
-        const unsigned nl = (unsigned)(gr.lq1 - gr.lq0);
-        if (pk)
-            k_list_heap<true><<<nl, 64, lds_h, s>>>(a.Ec, a.Bc, a.Ab, a.pool, a.lq + gr.lq0, (int)nl, k, m->id_base,
-                                                    m->oI.as<uint64_t>(), m->oD.as<float>(), m->oN.as<int32_t>());
-        else
-            k_list_heap<false><<<nl, 64, lds_h, s>>>(a.Ec, a.Bc, a.Ab, a.pool, a.lq + gr.lq0, (int)nl, k, m->id_base,
-                                                     m->oI.as<uint64_t>(), m->oD.as<float>(), m->oN.as<int32_t>());
-        HIPCHK(hipGetLastError());
+        for (int64_t q = 0; q < nq; q++) {
+            if (clo[(size_t)q] < 0) continue;
+            // k + 1 (or all) scores pairwise distinct: the first k are the reference's, whatever the heap's history
+            const int n = tN[(size_t)q];
+            const float* dq = tD.data() + (size_t)q * k1;
+            bool distinct = true;
+            for (int i = 0; i + 1 < n; i++) distinct = distinct && dq[i] < dq[i + 1];
+            if (!distinct) {
+                flagged[(size_t)q] = MVK_FLAG_TIE;
+                continue;
+            }
+            const int nk = std::min(n, (int)k);
+            std::copy(tI.begin() + (size_t)q * k1, tI.begin() + (size_t)q * k1 + nk, out_ids + (size_t)q * k);
+            std::copy(dq, dq + nk, out_dists + (size_t)q * k);
+            out_counts[q] = nk;
+        }
     }
-    if (m->timing) HIPCHK(hipEventRecord(m->ev1, s));
-    HIPCHK(hipMemcpyAsync(out_ids, m->oI.p, (size_t)nq * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(out_dists, m->oD.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(out_counts, m->oN.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (m->timing) {
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, m->ev0, m->ev1);
-        m->stats.last_kernel_ms = ms;
+    // the flagged queries and those that took no keys: today's call over their original lists
+    int64_t nrest = 0;
+    for (int64_t q = 0; q < nq; q++) {
+        const bool key = klo[(size_t)q] >= 0;
+        if (key && flagged[(size_t)q]) m->stats.last_fallback_queries++;
+        if (key && !flagged[(size_t)q]) lo[(size_t)q] = -1;
+        else nrest++;
+    }
+    if (nrest) {
+        tI.resize((size_t)nq * k);
+        tD.resize((size_t)nq * k);
+        rc = mv_exact_search(m, ids, lo.data(), hi.data(), nq, k, max_qv, true, tI.data(), tD.data(), tN.data());
+        if (rc) return rc;
+        for (int64_t q = 0; q < nq; q++) {
+            if (lo[(size_t)q] < 0) continue;
+            std::copy(tI.begin() + (size_t)q * k, tI.begin() + (size_t)(q + 1) * k, out_ids + (size_t)q * k);
+            std::copy(tD.begin() + (size_t)q * k, tD.begin() + (size_t)(q + 1) * k, out_dists + (size_t)q * k);
+            out_counts[q] = tN[(size_t)q];
+        }
     }
     return WV_OK;
 }
@@ -488,7 +800,47 @@ extern "C" int wv_mv_set_option(wv_mv* m, const char* key, int64_t value) {
         m->mv_tile = (int)value;
     } else if (k == "mv_list_rows") m->mv_list_rows = std::max<int64_t>(value, 0);
     else if (k == "timing") m->timing = value ? 1 : 0;
-    else return set_err(WV_ERR_INVALID, "unknown option %s", key);
+    else if (k == "mv_keys") {
+        if (value < -1 || value > 1) return set_err(WV_ERR_INVALID, "mv_keys: -1, 0 or 1");
+        m->mv_keys = (int)value;
+    } else if (k == "mv_keys_min") {
+        if (value < 0) return set_err(WV_ERR_INVALID, "mv_keys_min: 0 or more");
+        m->mv_keys_min = value;
+    } else if (k == "mv_keys_cap") {
+        if (value < 1 || value > INT32_MAX) return set_err(WV_ERR_INVALID, "mv_keys_cap: 1 or more");
+        m->mv_keys_cap = value;
+    } else return set_err(WV_ERR_INVALID, "unknown option %s", key);
+    return WV_OK;
+}
+
+extern "C" int wv_mv_debug_keys(wv_mv* m, int64_t q, float* keys, float* eps, uint32_t* slots, int64_t* n) {
+    if (!m || !n) return set_err(WV_ERR_INVALID, "nil index or count");
+    std::lock_guard<std::mutex> g(m->mu);
+    if (!m->kdbg) return set_err(WV_ERR_INVALID, "no key search to report");
+    size_t i = 0;
+    while (i < m->kplan.queries.size() && m->kplan.queries[i].q != q) i++;
+    if (i == m->kplan.queries.size()) return set_err(WV_ERR_INVALID, "query %lld took no keys", (long long)q);
+    const ListQuery& lq = m->kplan.queries[i];
+    *n = lq.len;
+    if (!keys || lq.len == 0) return WV_OK;
+    if (!eps || !slots) return set_err(WV_ERR_INVALID, "nil eps or slots");
+    HIPCHK(hipSetDevice(m->device));
+    const int64_t e0 = m->kabs[i], words = (lq.len + 63) / 64;
+    std::vector<uint64_t> ab((size_t)words);
+    std::vector<float> tm((size_t)m->hiwater);
+    HIPCHK(hipMemcpy(keys, m->Kc.as<float>() + e0, (size_t)lq.len * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ab.data(), m->kAb.as<uint64_t>() + e0 / 64, (size_t)words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tm.data(), m->tmax.p, tm.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < lq.len; j++) {
+        const uint32_t sl = m->kplan.pool[(size_t)(lq.pool_begin + j)];
+        slots[j] = sl;
+        if ((ab[(size_t)(j >> 6)] >> (j & 63)) & 1ull) {  // a listed slot without a document
+            keys[j] = __builtin_inff();
+            eps[j] = 0.f;
+        } else {
+            eps[j] = mvk_eps(m->h_cS[(size_t)q], tm[sl], keys[j]);
+        }
+    }
     return WV_OK;
 }
 

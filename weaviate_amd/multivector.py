@@ -86,6 +86,18 @@ class MultiVectorIndex:
         check(self._l.wv_mv_get_stats(self._h, C.byref(s)))
         return {f: getattr(s, f) for f, _ in s._fields_}
 
+    def debug_keys(self, q: int = 0):
+        """Diagnostic hook of the key route: (keys, eps, doc ids) of batch row q
+        of the last search that took keys, one entry per listed slot."""
+        n = C.c_int64(0)
+        check(self._l.wv_mv_debug_keys(self._h, int(q), None, None, None, C.byref(n)))
+        keys = np.zeros(max(n.value, 1), dtype=np.float32)
+        eps = np.zeros_like(keys)
+        slots = np.zeros(keys.size, dtype=np.uint32)
+        check(self._l.wv_mv_debug_keys(self._h, int(q), _fptr(keys), _fptr(eps),
+                                       slots.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n)))
+        return keys[: n.value], eps[: n.value], slots[: n.value].astype(np.uint64) + np.uint64(self.id_base)
+
     # -- insert path ------------------------------------------------------
     def add_multi(self, doc_id: int, vectors) -> None:
         self.add_multi_batch([doc_id], [vectors])
