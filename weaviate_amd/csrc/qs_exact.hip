@@ -4,7 +4,7 @@
 // (k_exact_bm) (see rt_index.h for the unit split).
 #include "rt_index.h"
 
-// k_blk_exact<RV, METRIC, VARIANT> over the queries of one chunk (list ==
+// k_blk_exact<RV, RT, METRIC, VARIANT> over the queries of one chunk (list ==
 // nullptr) or the listed ones; eb/ldE: block-major distances, capv: the per
 // query cap of the (k+1)-th exact distance (nullptr: uncapped)
 void launch_blk_exact(wv_index* idx, hipStream_t s, int RV, int metric, bool v5, const float* Qn,
@@ -18,20 +18,28 @@ void launch_blk_exact(wv_index* idx, hipStream_t s, int RV, int metric, bool v5,
     // int8 keys: the row bound from the int8 plane (q8f), else the bf16 plane
     Q8Filter f8{};
     if (q8f && idx->exact_filter && (Xb || idx->q8_only)) f8 = *q8f;
-#define WV_EXR(RV, M, V)                                                                                             \
+    // depth of the top lists under a finite cap: the 64 (RT - 1) >= k + 1 entries of qs_R_flat(k).  The
+    // list's full depth stays for kout = k + 1 (entry k is an output there, and its id among equal
+    // distances is only settled by a list longer than k + 1), for block-major distances (eb: the
+    // uncapped C2 path, its lists are read back, not computed) and for the 960-block and longer lists
+    // (RT == RV there but for the per-query second pass, which is rare)
+    const int RT = !eb && capv && kout <= k && RV <= 8 ? std::min(qs_R_flat(k), RV) : RV;
+#define WV_EXR(RV, RTV, M, V)                                                                                             \
     do {                                                                                                             \
-        if (eb) k_blk_exact<RV, M, V, true><<<(unsigned)cn, 256, 0, s>>>(idx->X, idx->dpad, valid, idx->hiwater, Qn, idx->dims, idx->qsCand.as<uint32_t>(), idx->qsNc.as<int32_t>(), cn, k, kout, idx->id_base, o_ids, o_d, o_n, flags, list, cnt, eb, ldE, capv, qinfo, Xb, idx->dpb, idx->xnorm2, idx->qsmax, idx->d_maxn2, gd, gacc_r, f8, nullptr, idx->cur_vq, idx->cur_tq, idx->qsEps.as<float>()); \
-        else k_blk_exact<RV, M, V, false><<<(unsigned)cn, 256, 0, s>>>(idx->X, idx->dpad, valid, idx->hiwater, Qn, idx->dims, idx->qsCand.as<uint32_t>(), idx->qsNc.as<int32_t>(), cn, k, kout, idx->id_base, o_ids, o_d, o_n, flags, list, cnt, nullptr, 0, capv, qinfo, Xb, idx->dpb, idx->xnorm2, idx->qsmax, idx->d_maxn2, gd, gacc_r, f8, fmask, idx->cur_vq, idx->cur_tq, idx->qsEps.as<float>()); \
+        if (eb) k_blk_exact<RV, RV, M, V, true><<<(unsigned)cn, 256, 0, s>>>(idx->X, idx->dpad, valid, idx->hiwater, Qn, idx->dims, idx->qsCand.as<uint32_t>(), idx->qsNc.as<int32_t>(), cn, k, kout, idx->id_base, o_ids, o_d, o_n, flags, list, cnt, eb, ldE, capv, qinfo, Xb, idx->dpb, idx->xnorm2, idx->qsmax, idx->d_maxn2, gd, gacc_r, f8, nullptr, idx->cur_vq, idx->cur_tq, idx->qsEps.as<float>()); \
+        else k_blk_exact<RV, RTV, M, V, false><<<(unsigned)cn, 256, 0, s>>>(idx->X, idx->dpad, valid, idx->hiwater, Qn, idx->dims, idx->qsCand.as<uint32_t>(), idx->qsNc.as<int32_t>(), cn, k, kout, idx->id_base, o_ids, o_d, o_n, flags, list, cnt, nullptr, 0, capv, qinfo, Xb, idx->dpb, idx->xnorm2, idx->qsmax, idx->d_maxn2, gd, gacc_r, f8, fmask, idx->cur_vq, idx->cur_tq, idx->qsEps.as<float>()); \
     } while (0)
-#define WV_EXM(RV)                                                          \
+#define WV_EXM(RV, RTV)                                                     \
     switch (metric) {                                                       \
-    case L2: if (v5) WV_EXR(RV, L2, AVX512); else WV_EXR(RV, L2, AVX256); break;   \
-    case DOT: if (v5) WV_EXR(RV, DOT, AVX512); else WV_EXR(RV, DOT, AVX256); break; \
-    default: if (v5) WV_EXR(RV, COSINE, AVX512); else WV_EXR(RV, COSINE, AVX256); break; \
+    case L2: if (v5) WV_EXR(RV, RTV, L2, AVX512); else WV_EXR(RV, RTV, L2, AVX256); break;   \
+    case DOT: if (v5) WV_EXR(RV, RTV, DOT, AVX512); else WV_EXR(RV, RTV, DOT, AVX256); break; \
+    default: if (v5) WV_EXR(RV, RTV, COSINE, AVX512); else WV_EXR(RV, RTV, COSINE, AVX256); break; \
     }
-    if (RV == 2) { WV_EXM(2); } else if (RV == 4) { WV_EXM(4); } else if (RV == 8) { WV_EXM(8); }
+    if (RV == 2) { WV_EXM(2, 2); }
+    else if (RV == 4) { if (RT == 2) { WV_EXM(4, 2); } else { WV_EXM(4, 4); } }
+    else if (RV == 8) { if (RT == 2) { WV_EXM(8, 2); } else if (RT == 4) { WV_EXM(8, 4); } else { WV_EXM(8, 8); } }
     else {  // k + 1 <= 960 / 1984 / 4032: never block-major (9-bit list positions)
-#define WV_EXB(RB, M, V) k_blk_exact<RB, M, V, false><<<(unsigned)cn, 256, 0, s>>>(idx->X, idx->dpad, valid, idx->hiwater, Qn, idx->dims, idx->qsCand.as<uint32_t>(), idx->qsNc.as<int32_t>(), cn, k, kout, idx->id_base, o_ids, o_d, o_n, flags, list, cnt, nullptr, 0, capv, qinfo, Xb, idx->dpb, idx->xnorm2, idx->qsmax, idx->d_maxn2, gd, gacc_r, f8, nullptr, idx->cur_vq, idx->cur_tq, idx->qsEps.as<float>())
+#define WV_EXB(RB, M, V) k_blk_exact<RB, RB, M, V, false><<<(unsigned)cn, 256, 0, s>>>(idx->X, idx->dpad, valid, idx->hiwater, Qn, idx->dims, idx->qsCand.as<uint32_t>(), idx->qsNc.as<int32_t>(), cn, k, kout, idx->id_base, o_ids, o_d, o_n, flags, list, cnt, nullptr, 0, capv, qinfo, Xb, idx->dpb, idx->xnorm2, idx->qsmax, idx->d_maxn2, gd, gacc_r, f8, nullptr, idx->cur_vq, idx->cur_tq, idx->qsEps.as<float>())
 #define WV_EXBM(RB)                                                                     \
         switch (metric) {                                                               \
         case L2: if (v5) WV_EXB(RB, L2, AVX512); else WV_EXB(RB, L2, AVX256); break;    \
@@ -51,8 +59,9 @@ void launch_blk_exact(wv_index* idx, hipStream_t s, int RV, int metric, bool v5,
 void launch_q8_filt_bm(wv_index* idx, hipStream_t s, int metric, const Q8Filter& f, const float* xn2,
                        const uint32_t* valid, int64_t nb, int L, const float* capv, const float4* qinfo, float gd,
                        uint32_t* fmask) {
-    const size_t lds = (size_t)(f.dpb8 >> 5) * 1024 + (size_t)8 * (f.dpb8 >> 5) * 32;
-#define WV_FB(M) k_q8_filt_bm<M><<<(unsigned)nb, 256, lds, s>>>(f, xn2, valid, idx->hiwater, idx->bmOff.as<uint32_t>(), idx->bmPairs.as<uint32_t>(), L, capv, qinfo, idx->d_maxn2, gd, fmask)
+    static_assert(FBM_NS == 3, "k_q8_filt_bm dispatches passes of 1, 2 or 3 listings per half-wave");
+    const size_t lds = (size_t)8 * FBM_NS * f.dpb8;  // 4 waves x 2 halves x FBM_NS queries' codes (<= 36 KiB)
+#define WV_FB(M) k_q8_filt_bm<M><<<(unsigned)((nb + 3) / 4), 256, lds, s>>>(f, xn2, valid, idx->hiwater, nb, idx->bmOff.as<uint32_t>(), idx->bmPairs.as<uint32_t>(), L, capv, qinfo, idx->d_maxn2, gd, fmask)
     switch (metric) {
     case L2: WV_FB(L2); break;
     case DOT: WV_FB(DOT); break;

@@ -1120,19 +1120,37 @@ __global__ __launch_bounds__(256) void k_blk_select_f(const float* __restrict__ 
         }
         nc = n2;
     };
+    // a 16-byte aligned key row is read as float4s: v[j] is key b0 + kid(j), four
+    // consecutive keys per lane and load.  The chunk of 64 U keys is the same set
+    // either way, and a chunk's offers all precede its appends, so M_cur and the T of
+    // any refresh inside the chunk are the chunk's, whatever the order within it.
+    // The prefix already appended at a mid-chunk refresh does differ with the
+    // order, but not the outcome: `over` fires exactly when more than CB keys up
+    // to and including this chunk qualify under that T, and otherwise the buffer
+    // after the chunk holds exactly those keys.
+    const bool vec = ((reinterpret_cast<uintptr_t>(key) | (uintptr_t)(ldk * sizeof(float))) & 15) == 0;
+    auto kid = [&](int j) { return vec ? (j >> 2) * 256 + lane * 4 + (j & 3) : j * 64 + lane; };
     for (int64_t b0 = 0; b0 < nb; b0 += 64 * U) {
         float v[U];
+        if (vec && b0 + 64 * U <= nb) {
 #pragma unroll
-        for (int j = 0; j < U; j++) {
-            const int64_t bb = b0 + j * 64 + lane;
-            v[j] = bb < nb ? kr[bb] : __builtin_inff();
+            for (int j = 0; j < U; j += 4) {
+                const float4 x = *reinterpret_cast<const float4*>(kr + b0 + kid(j));
+                v[j] = x.x; v[j + 1] = x.y; v[j + 2] = x.z; v[j + 3] = x.w;
+            }
+        } else {  // scalar rows and the ragged last chunk
+#pragma unroll
+            for (int j = 0; j < U; j++) {
+                const int64_t bb = b0 + kid(j);
+                v[j] = bb < nb ? kr[bb] : __builtin_inff();
+            }
         }
         bool any = false;
 #pragma unroll
         for (int j = 0; j < U; j++) any |= v[j] < t.thr;
         if (__any(any)) {
 #pragma unroll
-            for (int j = 0; j < U; j++) t.offer(v[j], (uint32_t)(b0 + j * 64 + lane), sbk[w], sbi[w], lane);
+            for (int j = 0; j < U; j++) t.offer(v[j], (uint32_t)(b0 + kid(j)), sbk[w], sbi[w], lane);
         }
         if (over) continue;
         bool anyc = false;  // one wave vote per chunk: most chunks append nothing
@@ -1155,7 +1173,7 @@ __global__ __launch_bounds__(256) void k_blk_select_f(const float* __restrict__ 
                 if (nc + n > CB) { over = true; break; }
             }
             const int pos = nc + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-            if (in) { cbk[w][pos] = v[j]; cbi[w][pos] = (uint32_t)(b0 + j * 64 + lane); }
+            if (in) { cbk[w][pos] = v[j]; cbi[w][pos] = (uint32_t)(b0 + kid(j)); }
             nc += n;
         }
     }
@@ -1519,13 +1537,20 @@ __device__ __forceinline__ float exact8_compact(const float* __restrict__ qv, co
     return dist;
 }
 
-// k_blk_exact<R, METRIC, VARIANT, EB>: one workgroup (4 waves) per query over its
+// k_blk_exact<R, RT, METRIC, VARIANT, EB>: one workgroup (4 waves) per query over its
 // candidate blocks (each wave two blocks per pass: lanes 0-31 and 32-63, lane
 // = row); EB: the distances come from k_exact_bm (ebuf).  Reference-order SingleDist of every valid row, top-(k+1) by
 // (distance, id) per wave, merged by wave 0; proof = the first min(k+1, n)
 // are strictly increasing (the reference heap then holds exactly the k
 // smallest and extractHeap returns them ascending).
-template <int R, int METRIC, int VARIANT, bool EB>
+// R is the stride of cand / fmask (L = 64 (R - 1) list positions per query); the
+// top lists are RT rows deep where the query's cap is finite: every row at or
+// above the cap is rejected at init(cap) and only entries 0..k are read (the
+// caller gives RT < R only with kout <= k and 64 (RT - 1) >= k + 1).  The list
+// code is a generic lambda instantiated at both depths; which one runs depends
+// on cap[q] alone, the same for every thread of the workgroup (one query per
+// workgroup), and the __syncthreads() inside relies on that.
+template <int R, int RT, int METRIC, int VARIANT, bool EB>
 __global__ __launch_bounds__(256) void k_blk_exact(const float* __restrict__ X, int dpad, const uint32_t* __restrict__ valid,
                                                    int64_t nrows, const float* __restrict__ Qn, int d,
                                                    const uint32_t* __restrict__ cand, const int32_t* __restrict__ ncand,
@@ -1591,104 +1616,111 @@ __global__ __launch_bounds__(256) void k_blk_exact(const float* __restrict__ X, 
         capq = cap[q];
         __syncthreads();
     }
-    WaveTopL<R> t;
-    t.init(cap ? cap[q] : __builtin_inff());  // only the k+1 smallest are used: nothing above cap
-    int nvalid = 0;
-    for (int j0 = 2 * w; j0 < nc; j0 += 8) {
-        const int j = j0 + lh;
-        bool ok = false;
-        int64_t row = 0;
-        if (j < nc) {
-            row = (int64_t)cand[(int64_t)q * L + j] * 32 + li;
-            ok = row < nrows && ((vrow[row >> 5] >> (row & 31)) & 1u);
-        }
-        float e = __builtin_inff();
-        if (EB) {  // its own instantiation: the distance code's registers stay out of the read-back form
-            if (ok) e = ebuf[(int64_t)q * ldE + j * 32 + li];
-        } else if (filt) {
-            const bool need = fm ? ok && ((fmask[(int64_t)q * L + (j < nc ? j : 0)] >> li) & 1u)
-                                 : ok && (f8 ? plane_a_q8<METRIC>(q8f.X8, q8f.sb8, xn2, row, q8f.dpb8, sq8, sqs, qi.x)
-                                             : plane_a<METRIC>(Xb, xn2, row, dpb, sqh, qi.x)) - eps_r < capq;
-            const float dl = coop ? exact8_compact<METRIC>(qv, X, dpad, d, row, need, lane, sslot[w])
-                                  : need ? exact_dist<METRIC, VARIANT>(qv, X + row * dpad, d) : 0.f;
-            if (need) e = dl;
-        } else if (coop) {  // 8 lanes per row, rows 8g + (lane >> 3) of the pass
-            const float* xp[8];
-#pragma unroll
-            for (int g = 0; g < 8; g++) {
-                const int r = 8 * g + (lane >> 3);
-                const int jg = r >= 32 && j0 + 1 < nc ? j0 + 1 : j0;
-                const int64_t rw = (int64_t)cand[(int64_t)q * L + jg] * 32 + (r & 31);
-                xp[g] = X + (rw < nrows ? rw : 0) * dpad;
+    auto body = [&](auto depth) {
+        constexpr int D = decltype(depth)::value;
+        WaveTopL<D> t;
+        t.init(cap ? cap[q] : __builtin_inff());  // only the k+1 smallest are used: nothing above cap
+        int nvalid = 0;
+        for (int j0 = 2 * w; j0 < nc; j0 += 8) {
+            const int j = j0 + lh;
+            bool ok = false;
+            int64_t row = 0;
+            if (j < nc) {
+                row = (int64_t)cand[(int64_t)q * L + j] * 32 + li;
+                ok = row < nrows && ((vrow[row >> 5] >> (row & 31)) & 1u);
             }
-            const float dl = exact8_rows64<METRIC>(qv, xp, d, lane);
-            if (ok) e = dl;
-        } else if (ok) {
-            e = exact_dist<METRIC, VARIANT>(qv, X + row * dpad, d);
+            float e = __builtin_inff();
+            if (EB) {  // its own instantiation: the distance code's registers stay out of the read-back form
+                if (ok) e = ebuf[(int64_t)q * ldE + j * 32 + li];
+            } else if (filt) {
+                const bool need = fm ? ok && ((fmask[(int64_t)q * L + (j < nc ? j : 0)] >> li) & 1u)
+                                     : ok && (f8 ? plane_a_q8<METRIC>(q8f.X8, q8f.sb8, xn2, row, q8f.dpb8, sq8, sqs, qi.x)
+                                                 : plane_a<METRIC>(Xb, xn2, row, dpb, sqh, qi.x)) - eps_r < capq;
+                const float dl = coop ? exact8_compact<METRIC>(qv, X, dpad, d, row, need, lane, sslot[w])
+                                      : need ? exact_dist<METRIC, VARIANT>(qv, X + row * dpad, d) : 0.f;
+                if (need) e = dl;
+            } else if (coop) {  // 8 lanes per row, rows 8g + (lane >> 3) of the pass
+                const float* xp[8];
+#pragma unroll
+                for (int g = 0; g < 8; g++) {
+                    const int r = 8 * g + (lane >> 3);
+                    const int jg = r >= 32 && j0 + 1 < nc ? j0 + 1 : j0;
+                    const int64_t rw = (int64_t)cand[(int64_t)q * L + jg] * 32 + (r & 31);
+                    xp[g] = X + (rw < nrows ? rw : 0) * dpad;
+                }
+                const float dl = exact8_rows64<METRIC>(qv, xp, d, lane);
+                if (ok) e = dl;
+            } else if (ok) {
+                e = exact_dist<METRIC, VARIANT>(qv, X + row * dpad, d);
+            }
+            nvalid += __popcll(__ballot(ok));
+            t.offer(ok ? e : __builtin_inff(), ok ? (uint32_t)row : NO_ID, sbk[w], sbi[w], lane);
         }
-        nvalid += __popcll(__ballot(ok));
-        t.offer(ok ? e : __builtin_inff(), ok ? (uint32_t)row : NO_ID, sbk[w], sbi[w], lane);
-    }
-    t.merge(sbk[w], sbi[w], lane);
-    if (w > 0) {
+        t.merge(sbk[w], sbi[w], lane);
+        if (w > 0) {
 #pragma unroll
-        for (int r = 0; r < R - 1; r++) {
-            lk[w - 1][r * 64 + lane] = t.key[r];
-            lid[w - 1][r * 64 + lane] = t.id[r];
+            for (int r = 0; r < D - 1; r++) {
+                lk[w - 1][r * 64 + lane] = t.key[r];
+                lid[w - 1][r * 64 + lane] = t.id[r];
+            }
         }
-    }
-    if (lane == 0) snv[w] = nvalid;
-    __syncthreads();
-    if (w > 0) return;
-    // wave 0: merge the other waves' lists into its own
-    for (int w2 = 0; w2 < 3; w2++)
-        for (int r = 0; r < R - 1; r++) t.offer(lk[w2][r * 64 + lane], lid[w2][r * 64 + lane], sbk[0], sbi[0], lane);
-    t.merge(sbk[0], sbi[0], lane);
-    nvalid = snv[0] + snv[1] + snv[2] + snv[3];
-    // with a finite cap the list holds exactly the rows below it (the others
-    // were skipped or rejected): a shard's cap in the sharded phase 2 may leave
-    // fewer than k+1 (the global top-(k+1) rows are all below it)
-    if (cap && cap[q] < __builtin_inff()) {
-        int nb = 0;
+        if (lane == 0) snv[w] = nvalid;
+        __syncthreads();
+        if (w > 0) return;
+        // wave 0: merge the other waves' lists into its own
+        for (int w2 = 0; w2 < 3; w2++)
+            for (int r = 0; r < D - 1; r++) t.offer(lk[w2][r * 64 + lane], lid[w2][r * 64 + lane], sbk[0], sbi[0], lane);
+        t.merge(sbk[0], sbi[0], lane);
+        nvalid = snv[0] + snv[1] + snv[2] + snv[3];
+        // with a finite cap the list holds exactly the rows below it (the others
+        // were skipped or rejected): a shard's cap in the sharded phase 2 may leave
+        // fewer than k+1 (the global top-(k+1) rows are all below it)
+        if (cap && cap[q] < __builtin_inff()) {
+            int nb = 0;
 #pragma unroll
-        for (int r = 0; r < R - 1; r++) nb += __popcll(__ballot(t.key[r] < __builtin_inff()));
-        nvalid = nb < nvalid ? nb : nvalid;
-    }
-    const int m = (k + 1) < nvalid ? (k + 1) : nvalid;
-    bool inc = true;
-#pragma unroll
-    for (int r = 0; r < R - 1; r++) {
-        const float up = __shfl_up(t.key[r], 1);
-        const float wrap = (r > 0) ? __shfl(t.key[r > 0 ? r - 1 : 0], 63) : 0.f;
-        const float pv = lane == 0 ? wrap : up;
-        const int e = r * 64 + lane;
-        if (e >= 1 && e < m && !(t.key[r] > pv)) inc = false;
-    }
-    inc = __all(inc);
-    // per-query allow bitmaps (vq): the keys came from their union, so the
-    // k+1 blocks under M need not hold k+1 of this query's rows.  Rows of
-    // unlisted blocks are > T - eps (A > T there, E >= A - eps): the list is
-    // complete when it holds k+1 rows and its (k+1)-th is <= T - eps (the
-    // rounded difference one ulp down: below the exact one); else the replay
-    // decides.  T = inf: every block with a union row is listed.
-    // The same test for a list whose threshold was lowered below the L-th key
-    // (k_blk_select: more blocks than the list qualified).
-    if (tq && inc && tq[q] < __builtin_inff())
-        inc = nvalid >= k + 1 && t.key_at(k) <= qs_next_down(tq[q] - qeps[q]);
-    if (!inc) {
-        if (lane == 0) flags[q] = 1;
-        return;
-    }
-    const int nout = kout < nvalid ? kout : nvalid;
-#pragma unroll
-    for (int r = 0; r < R - 1; r++) {
-        const int e = r * 64 + lane;
-        if (e < nout) {
-            out_ids[(int64_t)q * kout + e] = id_base + t.id[r];
-            out_d[(int64_t)q * kout + e] = t.key[r];
+            for (int r = 0; r < D - 1; r++) nb += __popcll(__ballot(t.key[r] < __builtin_inff()));
+            nvalid = nb < nvalid ? nb : nvalid;
         }
+        const int m = (k + 1) < nvalid ? (k + 1) : nvalid;
+        bool inc = true;
+#pragma unroll
+        for (int r = 0; r < D - 1; r++) {
+            const float up = __shfl_up(t.key[r], 1);
+            const float wrap = (r > 0) ? __shfl(t.key[r > 0 ? r - 1 : 0], 63) : 0.f;
+            const float pv = lane == 0 ? wrap : up;
+            const int e = r * 64 + lane;
+            if (e >= 1 && e < m && !(t.key[r] > pv)) inc = false;
+        }
+        inc = __all(inc);
+        // per-query allow bitmaps (vq): the keys came from their union, so the
+        // k+1 blocks under M need not hold k+1 of this query's rows.  Rows of
+        // unlisted blocks are > T - eps (A > T there, E >= A - eps): the list is
+        // complete when it holds k+1 rows and its (k+1)-th is <= T - eps (the
+        // rounded difference one ulp down: below the exact one); else the replay
+        // decides.  T = inf: every block with a union row is listed.
+        // The same test for a list whose threshold was lowered below the L-th key
+        // (k_blk_select: more blocks than the list qualified).
+        if (tq && inc && tq[q] < __builtin_inff())
+            inc = nvalid >= k + 1 && t.key_at(k) <= qs_next_down(tq[q] - qeps[q]);
+        if (!inc) {
+            if (lane == 0) flags[q] = 1;
+            return;
+        }
+        const int nout = kout < nvalid ? kout : nvalid;
+#pragma unroll
+        for (int r = 0; r < D - 1; r++) {
+            const int e = r * 64 + lane;
+            if (e < nout) {
+                out_ids[(int64_t)q * kout + e] = id_base + t.id[r];
+                out_d[(int64_t)q * kout + e] = t.key[r];
+            }
+        }
+        if (lane == 0) out_n[q] = nout;
+    };
+    if constexpr (RT < R) {
+        if (cap && cap[q] < __builtin_inff()) return body(std::integral_constant<int, RT>{});
     }
-    if (lane == 0) out_n[q] = nout;
+    body(std::integral_constant<int, R>{});
 }
 
 // ---------------------------------------------------------------------------
@@ -1820,68 +1852,130 @@ __global__ __launch_bounds__(256) void k_exact_bm(const float* __restrict__ X, i
 // Block-major int8 row filter of the capped exact pass (int8 block keys,
 // int8 rows of up to 1536 columns).  Candidate-major, every listing query
 // re-reads its candidate block's codes from HBM (C3: ~920k listings over
-// ~312k distinct blocks per 8192-query batch, 22.6 GB); here one workgroup per
-// listed 32-row block (the k_inv_* inversion) stages the block's codes in LDS
-// once and gives every listing (query, list position) the 32 rows' survivor
-// mask: bit r = row r is valid and A_row - eps_r < cap(q), with A_row the
-// same float arithmetic as plane_a_q8 (so the same rows survive).  LDS:
-// [chunk][32 rows][32 B] block codes, then per wave two listings' query codes.
+// ~312k distinct blocks per 8192-query batch, 22.6 GB); here every listed
+// 32-row block (the k_inv_* inversion) is read once per pass of up to
+// 2 FBM_NS listings and gives every listing (query, list position) the 32
+// rows' survivor mask: bit r = row r is valid and A_row - eps_r < cap(q), with
+// A_row the same float arithmetic as plane_a_q8 (so the same rows survive).
+// One wave per block, four blocks per workgroup and no workgroup barrier (a
+// wave whose block nobody lists leaves at once): lane = row in both halves of
+// the wave, half h scores the listings pb + 2 s + h, s < NS.  The block's
+// codes go from global memory to registers chunk by chunk (1 KiB contiguous
+// per chunk in the tiled plane) and meet the codes of all the pass's queries,
+// which wait in LDS ([wave][half][slot][dpb8] bytes) before the dot loop.
+// A block with more than 2 FBM_NS listings reads its codes again from global
+// memory (L2) in every further pass, where a staged copy would be read from
+// LDS: nothing at C3's ~3 listings per block, one re-read per 6 listings for
+// heavily listed blocks (small indexes under large batches).  A half-wave
+// without a listing in a slot loads and scores the pass's first query again
+// and writes no mask.
+constexpr int FBM_NS = 3;
+
+template <int METRIC, int NS>
+__device__ __forceinline__ void q8_filt_pass(const Q8Filter& f, const unsigned char* __restrict__ xrow, int nch,
+                                             uint4* qs, uint32_t pb, uint32_t p1, const uint32_t* __restrict__ pairs,
+                                             int li, int lh, bool okr, float sbk, float x2, int L,
+                                             const float* __restrict__ cap, const float4* __restrict__ qinfo,
+                                             const uint32_t* __restrict__ maxn2, float gd,
+                                             uint32_t* __restrict__ fmask) {
+    // the block's first four chunks are on their way while the pairs and the query codes arrive
+    const int ng = nch >> 2;
+    uint4 nx[8];
+    auto load4 = [&](int g) {
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint4* xp = reinterpret_cast<const uint4*>(xrow + (int64_t)(4 * g + u) * 8192);
+            nx[2 * u] = xp[0];
+            nx[2 * u + 1] = xp[1];
+        }
+    };
+    if (ng) load4(0);
+    int64_t q[NS];
+    int j[NS];
+    bool has[NS];
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        const uint32_t p = pb + 2 * s + lh;
+        has[s] = p < p1;
+        const uint32_t pr = pairs[has[s] ? p : pb];  // a half without a listing repeats the pass's first
+        q[s] = pr >> 9;
+        j[s] = (int)(pr & 511u);
+    }
+#pragma unroll
+    for (int s = 0; s < NS; s++)
+        for (int i = li; i < nch * 2; i += 32)
+            qs[s * nch * 2 + i] = *reinterpret_cast<const uint4*>(f.Q8 + ((q[s] >> 8) * nch + (i >> 1)) * 8192 +
+                                                                   (q[s] & 255) * 32 + (i & 1) * 16);
+    wave_sync_lds();
+    int acc[NS];
+#pragma unroll
+    for (int s = 0; s < NS; s++) acc[s] = 0;
+    auto dots = [&](int c, const uint4& v0, const uint4& v1) {
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            const uint4 a0 = qs[(s * nch + c) * 2], a1 = qs[(s * nch + c) * 2 + 1];
+            acc[s] = __builtin_amdgcn_sdot4((int)v0.x, (int)a0.x, acc[s], false);
+            acc[s] = __builtin_amdgcn_sdot4((int)v0.y, (int)a0.y, acc[s], false);
+            acc[s] = __builtin_amdgcn_sdot4((int)v0.z, (int)a0.z, acc[s], false);
+            acc[s] = __builtin_amdgcn_sdot4((int)v0.w, (int)a0.w, acc[s], false);
+            acc[s] = __builtin_amdgcn_sdot4((int)v1.x, (int)a1.x, acc[s], false);
+            acc[s] = __builtin_amdgcn_sdot4((int)v1.y, (int)a1.y, acc[s], false);
+            acc[s] = __builtin_amdgcn_sdot4((int)v1.z, (int)a1.z, acc[s], false);
+            acc[s] = __builtin_amdgcn_sdot4((int)v1.w, (int)a1.w, acc[s], false);
+        }
+    };
+    for (int g = 0; g < ng; g++) {  // four chunks in registers, the next four in flight
+        uint4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = nx[u];
+        if (g + 1 < ng) load4(g + 1);
+#pragma unroll
+        for (int u = 0; u < 4; u++) dots(4 * g + u, v[2 * u], v[2 * u + 1]);
+    }
+    for (int c = 4 * ng; c < nch; c++) {
+        const uint4* xp = reinterpret_cast<const uint4*>(xrow + (int64_t)c * 8192);
+        dots(c, xp[0], xp[1]);
+    }
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        const float eps_r = qs_eps(METRIC == COSINE ? COSINE : METRIC == DOT ? DOT : L2, f.qinfo8[q[s]], f.qmax8, maxn2,
+                                   gd, f.gacc8);
+        const float sc = f.qscale[q[s]] * sbk;
+        const float Sf = (float)acc[s];
+        const float kv = METRIC == L2 ? fmaf(-2.f * sc, Sf, x2) : -(sc * Sf);
+        const float A = qs_key_to_a(METRIC == COSINE ? COSINE : METRIC == DOT ? DOT : L2, kv, qinfo[q[s]].x);
+        const uint64_t m = __ballot(okr && A - eps_r < cap[q[s]]);
+        if (has[s] && li == 0) fmask[q[s] * L + j[s]] = (uint32_t)(m >> (32 * lh));
+    }
+    wave_sync_lds();  // the next pass's codes overwrite qs
+}
+
 template <int METRIC>
 __global__ __launch_bounds__(256) void k_q8_filt_bm(const Q8Filter f, const float* __restrict__ xn2,
-                                                    const uint32_t* __restrict__ valid, int64_t nrows,
+                                                    const uint32_t* __restrict__ valid, int64_t nrows, int64_t nb,
                                                     const uint32_t* __restrict__ off, const uint32_t* __restrict__ pairs,
                                                     int L, const float* __restrict__ cap,
                                                     const float4* __restrict__ qinfo,
                                                     const uint32_t* __restrict__ maxn2, float gd,
                                                     uint32_t* __restrict__ fmask) {
     extern __shared__ uint4 fsm4[];
-    const int64_t b = blockIdx.x;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 31, lh = lane >> 5;
+    const int64_t b = (int64_t)blockIdx.x * 4 + w;
+    if (b >= nb) return;
     const uint32_t p0 = off[b], p1 = off[b + 1];
     if (p0 == p1) return;
-    const int t = threadIdx.x;
     const int nch = f.dpb8 >> 5;  // 32-byte column chunks
-    // the block's rows are 1 KiB contiguous per chunk in the tiled plane
-    const uint4* src = reinterpret_cast<const uint4*>(f.X8 + (b >> 3) * (int64_t)f.dpb8 * 256 + (b & 7) * 1024);
-    for (int i = t; i < nch * 64; i += 256) fsm4[i] = src[(int64_t)(i >> 6) * 512 + (i & 63)];
-    const int lane = t & 63, w = t >> 6, li = lane & 31, lh = lane >> 5;
-    uint4* qs = fsm4 + nch * 64 + (w * 2 + lh) * nch * 2;
+    uint4* qs = fsm4 + (w * 2 + lh) * FBM_NS * nch * 2;
+    const unsigned char* xrow = f.X8 + (b >> 3) * (int64_t)f.dpb8 * 256 + (b & 7) * 1024 + li * 32;
     const int64_t row = b * 32 + li;
     const bool okr = row < nrows && ((valid[row >> 5] >> li) & 1u);
     const float sbk = f.sb8[b];
     const float x2 = METRIC == L2 ? xn2[row] : 0.f;
-    __syncthreads();
-    for (uint32_t pb = p0 + 2 * w; pb < p1; pb += 8) {
-        const uint32_t p = pb + lh;
-        const bool has = p < p1;
-        const uint32_t pr = pairs[has ? p : pb];
-        const int64_t q = pr >> 9;
-        const int j = (int)(pr & 511u);
-        for (int i = li; i < nch * 2; i += 32)
-            qs[i] = *reinterpret_cast<const uint4*>(f.Q8 + ((q >> 8) * nch + (i >> 1)) * 8192 + (q & 255) * 32 +
-                                                    (i & 1) * 16);
-        wave_sync_lds();
-        int acc = 0;
-        for (int c = 0; c < nch; c++) {
-            const uint4 v0 = fsm4[c * 64 + li * 2], v1 = fsm4[c * 64 + li * 2 + 1];
-            const uint4 a0 = qs[2 * c], a1 = qs[2 * c + 1];
-            acc = __builtin_amdgcn_sdot4((int)v0.x, (int)a0.x, acc, false);
-            acc = __builtin_amdgcn_sdot4((int)v0.y, (int)a0.y, acc, false);
-            acc = __builtin_amdgcn_sdot4((int)v0.z, (int)a0.z, acc, false);
-            acc = __builtin_amdgcn_sdot4((int)v0.w, (int)a0.w, acc, false);
-            acc = __builtin_amdgcn_sdot4((int)v1.x, (int)a1.x, acc, false);
-            acc = __builtin_amdgcn_sdot4((int)v1.y, (int)a1.y, acc, false);
-            acc = __builtin_amdgcn_sdot4((int)v1.z, (int)a1.z, acc, false);
-            acc = __builtin_amdgcn_sdot4((int)v1.w, (int)a1.w, acc, false);
-        }
-        const float eps_r = qs_eps(METRIC == COSINE ? COSINE : METRIC == DOT ? DOT : L2, f.qinfo8[q], f.qmax8, maxn2,
-                                   gd, f.gacc8);
-        const float s = f.qscale[q] * sbk;
-        const float Sf = (float)acc;
-        const float kv = METRIC == L2 ? fmaf(-2.f * s, Sf, x2) : -(s * Sf);
-        const float A = qs_key_to_a(METRIC == COSINE ? COSINE : METRIC == DOT ? DOT : L2, kv, qinfo[q].x);
-        const uint64_t m = __ballot(okr && A - eps_r < cap[q]);
-        if (has && li == 0) fmask[q * L + j] = (uint32_t)(m >> (32 * lh));
-        wave_sync_lds();  // the next listings' codes overwrite qs
+    for (uint32_t pb = p0; pb < p1; pb += 2 * FBM_NS) {
+        const uint32_t ns = (p1 - pb + 1) / 2;
+#define WV_FP(NSV) q8_filt_pass<METRIC, NSV>(f, xrow, nch, qs, pb, p1, pairs, li, lh, okr, sbk, x2, L, cap, qinfo, maxn2, gd, fmask)
+        if (ns >= 3) WV_FP(3); else if (ns == 2) WV_FP(2); else WV_FP(1);
+#undef WV_FP
     }
 }
 
