@@ -3,7 +3,9 @@ the host: tools/key_plan_print.cpp compiled against the header, its plans
 compared with values worked out from the three hand-written copies of the
 arithmetic the header replaced.  The rows where the 4 GiB buffer-offset bound
 binds (10^8 slots, 6144-byte rows, 3 * 10^7 slots with a `spans` option) are
-out of any GPU test's reach: this is their only check."""
+out of any GPU test's reach: this is their only check.  ring_span_plan (the
+rq-8 / rq-1 / SQ ring) against rows evaluated from the formula both
+*_candidates functions carried before it."""
 import os
 import shutil
 import subprocess
@@ -30,12 +32,31 @@ TABLE = [
     (1, 30000000, 2, 512, 3, True, 131005, 229),
 ]
 
+# nqg, nblk -> blocks per span, nspans
+RING_TABLE = [
+    (1, 1, 1, 1),
+    (1, 15, 15, 1),
+    (1, 33, 17, 2),
+    (3, 1000, 17, 59),
+    (1, 31250, 17, 1839),
+    (4, 31250, 62, 505),
+    (16, 312500, 2442, 128),
+    (32, 3125000, 48829, 64),
+    (2048, 31250, 31250, 1),
+    (4096, 64, 64, 1),
+]
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
-def test_key_plan_table(tmp_path):
+
+def build_tool(tmp_path):
     exe = str(tmp_path / "key_plan_print")
     subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(REPO, "tools", "key_plan_print.cpp"),
                     "-o", exe], check=True)
+    return exe
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_key_plan_table(tmp_path):
+    exe = build_tool(tmp_path)
     rows = "".join(f"{nqg} {nslots} {rb} {rowb} {spans} {int(whole)}\n" for nqg, nslots, rb, rowb, spans, whole, _, _ in TABLE)
     out = subprocess.run([exe], input=rows, capture_output=True, text=True, check=True).stdout.split("\n")
     got = [tuple(int(x) for x in line.split()) for line in out if line]
@@ -43,3 +64,15 @@ def test_key_plan_table(tmp_path):
     for row, plan in zip(TABLE, got):
         print(row[:6], "->", plan)
         assert plan == row[6:], f"key_plan{row[:6]} = {plan}, expected {row[6:]}"
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_ring_span_plan_table(tmp_path):
+    exe = build_tool(tmp_path)
+    rows = "".join(f"{nqg} {nblk}\n" for nqg, nblk, _, _ in RING_TABLE)
+    out = subprocess.run([exe, "ring"], input=rows, capture_output=True, text=True, check=True).stdout.split("\n")
+    got = [tuple(int(x) for x in line.split()) for line in out if line]
+    assert len(got) == len(RING_TABLE)
+    for row, plan in zip(RING_TABLE, got):
+        print(row[:2], "->", plan)
+        assert plan == row[2:], f"ring_span_plan{row[:2]} = {plan}, expected {row[2:]}"

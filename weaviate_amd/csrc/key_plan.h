@@ -2,6 +2,7 @@
 // nothing from HIP).  A key kernel's grid is nqg query groups x nspans spans of
 // slots_per_span ring slots (RB 32-row blocks each); search_qs (bf16 and int8
 // keys), the PQ int8 keys and the BQ block minima all take their split here.
+// The rq-8 / rq-1 / SQ ring has a rule of its own, ring_span_plan below.
 //
 // The rule:
 //   1. start from 256 / gcd(256, nqg) spans and double until nqg * nspans >= 256
@@ -39,4 +40,18 @@ inline KeyPlan key_plan(int nqg, int64_t nslots, int rb, int64_t row_bytes, int 
     nspans = std::max<int64_t>(1, std::min<int64_t>(nspans, nslots));
     const int64_t sps = (nslots + nspans - 1) / nspans;
     return KeyPlan{(int)sps, (int)((nslots + sps - 1) / sps)};
+}
+
+// The rq-8 / rq-1 / SQ ring (i8_ring_keys): nqg query groups x nspans spans of
+// blocks_per_span 32-row blocks.  ~2048 workgroups (8 per CU), at least 16
+// blocks each; the spans left empty are dropped.
+struct RingSpanPlan {
+    int blocks_per_span;
+    int nspans;
+};
+
+inline RingSpanPlan ring_span_plan(int nqg, int64_t nblk) {
+    const int64_t nspans = std::max<int64_t>(1, std::min<int64_t>(nblk / 16, (2048 + nqg - 1) / nqg));
+    const int64_t bps = (nblk + nspans - 1) / nspans;
+    return RingSpanPlan{(int)bps, (int)((nblk + bps - 1) / bps)};
 }

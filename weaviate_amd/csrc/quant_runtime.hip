@@ -2021,19 +2021,6 @@ bool rq_pqa_route(const wv_index* idx, int64_t nq, int k) {
     return rq_pqa_max(idx, k) > 0 && rq8_one_chunk(idx, nq);
 }
 
-template <int NC>
-static void launch_rq8_keys(const RQ8Args& a, unsigned grid, hipStream_t s, int bits) {
-    constexpr size_t lds = (size_t)rq8_nbuf(NC) * ((size_t)32 * 64 * NC + 656);  // the ring (k_rq8_keys)
-    // a refused limit is not checked here: the launch then fails, and the caller reads that error
-    if (bits == 8) {
-        (void)set_dyn_lds((const void*)k_rq8_keys<NC, 8>, lds);
-        k_rq8_keys<NC, 8><<<grid, 512, lds, s>>>(a);
-    } else {
-        (void)set_dyn_lds((const void*)k_rq8_keys<NC, 1>, lds);
-        k_rq8_keys<NC, 1><<<grid, 512, lds, s>>>(a);
-    }
-}
-
 // exact rq-8 block minima -> candidate blocks -> exact distances of their
 // rows: the ascending R-lists (ascI / ascD / ascN) of every query, oF[q] = 1
 // where a tie or a NaN leaves the heap's order to the replay.  own != NULL: a
@@ -2088,76 +2075,41 @@ static int rq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const
     const int QG = NC > 16 ? rq8_wide_queries(NC) : 256;  // queries per workgroup (both divide the padding)
     idx->rq_dbg_nq = std::min<int64_t>(QC, nq);
     idx->rq_dbg_nb = nblk;
-    for (int64_t c0 = 0; c0 < nq; c0 += QC) {
-        const int64_t cn = std::min<int64_t>(QC, nq - c0);
-        const int64_t cpad = round_up(cn, 256);
-        a.Qp = Qp + c0 * D;
-        a.qmeta = Qm + c0;
-        a.qcsum = Qcs + c0;
-        a.nqg = (int)(cpad / QG);
-        // spans: ~2048 workgroups (8 per CU), at least 16 blocks each
-        int64_t nspans = std::max<int64_t>(1, std::min<int64_t>(nblk / 16, (2048 + a.nqg - 1) / a.nqg));
-        const int64_t bps = (nblk + nspans - 1) / nspans;
-        nspans = (nblk + bps - 1) / bps;
-        a.blocks_per_span = (int)bps;
-        a.nspans = (int)nspans;
-        const unsigned grid = (unsigned)(a.nqg * nspans);
-        const bool time_it = idx->timing && c0 == 0;
-        if (time_it) HIPCHK(hipEventRecord(idx->ev0, s));
-        if (NC > 16) HIPCHK((hipError_t)wv_rq8_keys_wide(a, s, bits));
-        else switch (NC) {
-        case 1: launch_rq8_keys<1>(a, grid, s, bits); break;
-        case 2: launch_rq8_keys<2>(a, grid, s, bits); break;
-        case 3: launch_rq8_keys<3>(a, grid, s, bits); break;
-        case 4: launch_rq8_keys<4>(a, grid, s, bits); break;
-        case 5: launch_rq8_keys<5>(a, grid, s, bits); break;
-        case 6: launch_rq8_keys<6>(a, grid, s, bits); break;
-        case 7: launch_rq8_keys<7>(a, grid, s, bits); break;
-        case 8: launch_rq8_keys<8>(a, grid, s, bits); break;
-        case 9: launch_rq8_keys<9>(a, grid, s, bits); break;
-        case 10: launch_rq8_keys<10>(a, grid, s, bits); break;
-        case 11: launch_rq8_keys<11>(a, grid, s, bits); break;
-        case 12: launch_rq8_keys<12>(a, grid, s, bits); break;
-        case 13: launch_rq8_keys<13>(a, grid, s, bits); break;
-        case 14: launch_rq8_keys<14>(a, grid, s, bits); break;
-        case 15: launch_rq8_keys<15>(a, grid, s, bits); break;
-        default: launch_rq8_keys<16>(a, grid, s, bits); break;
-        }
-        HIPCHK(hipGetLastError());
-        if (time_it) HIPCHK(hipEventRecord(idx->ev1, s));
-        const unsigned gw = (unsigned)((cn + 3) / 4);
-        uint32_t* cand = idx->qsCand.as<uint32_t>() + c0 * Lc;
-        int32_t* ncand = idx->qsNc.as<int32_t>() + c0;
-        int32_t* of = idx->oF.as<int32_t>() + c0;
-        const size_t lq = (size_t)4 * (bits == 8 ? D : (5 * (D / 64) + 1) / 2 * 16);
-        const void* qsrc = bits == 8 ? (const void*)a.Qp : idx->rqq.p;
-        float* mq = own ? idx->rq8M.as<float>() + c0 : nullptr;
-#define WV_RQC(RTV, B, PQV)                                                                                           \
-    k_rq8_cand<RTV, B, PQV><<<gw, 256, lq, s>>>(idx->rq_codes, idx->cap, idx->rq_meta, PQV ? own : valid,              \
-                                                idx->hiwater, qsrc, c0, a.qmeta, D, fl2, fcos, cand, Lc, ncand,      \
-                                                (int)cn, R, idx->id_base, idx->ascI.as<uint64_t>() + c0 * R,         \
-                                                idx->ascD.as<float>() + c0 * R, idx->ascN.as<int32_t>() + c0, of,    \
-                                                own_vq, mq)
-#define WV_RQP(RTV, PQV)                                                                                              \
-    do {                                                                                                              \
-        k_rq8_sel<RTV, PQV><<<gw, 256, 0, s>>>(a.key, nblk, nblk, (int)cn, R, cand, Lc, ncand, of, mq);               \
-        if (bits == 8) WV_RQC(RTV, 8, PQV);                                                                            \
-        else WV_RQC(RTV, 1, PQV);                                                                                      \
-    } while (0)
-#define WV_RQ8(RTV)                  \
-    do {                             \
-        if (own) WV_RQP(RTV, true);  \
-        else WV_RQP(RTV, false);     \
-    } while (0)
-        if (RT == 2) WV_RQ8(2);
-        else if (RT == 4) WV_RQ8(4);
-        else if (RT == 8) WV_RQ8(8);
-        else WV_RQ8(16);
-#undef WV_RQ8
-#undef WV_RQP
-#undef WV_RQC
-        HIPCHK(hipGetLastError());
-    }
+    const size_t lq = (size_t)4 * (bits == 8 ? D : (5 * (D / 64) + 1) / 2 * 16);
+    const int rc = ring_query_chunks(
+        idx, s, nq, QC, QG, Lc, a,
+        [&](int64_t c0, unsigned grid) {
+            a.Qp = Qp + c0 * D;
+            a.qmeta = Qm + c0;
+            a.qcsum = Qcs + c0;
+            if (NC > 16) HIPCHK((hipError_t)wv_rq8_keys_wide(a, s, bits));
+            else if (bits == 8) launch_ring_keys<RQ8Codec<8>>(a, NC, grid, s);
+            else launch_ring_keys<RQ8Codec<1>>(a, NC, grid, s);
+            return (int)WV_OK;
+        },
+        [&](int64_t c0, int64_t cn, unsigned gw, uint32_t* cand, int32_t* ncand, int32_t* of) {
+            const void* qsrc = bits == 8 ? (const void*)a.Qp : idx->rqq.p;
+            float* mq = own ? idx->rq8M.as<float>() + c0 : nullptr;
+            // the select and the candidates' rows for the list size, the bit width and (own) the multi-allow form
+            auto run = [&](auto rt, auto b, auto pq) {
+                constexpr int RTV = decltype(rt)::value, B = decltype(b)::value;
+                constexpr bool PQV = decltype(pq)::value;
+                k_rq8_sel<RTV, PQV><<<gw, 256, 0, s>>>(a.key, nblk, nblk, (int)cn, R, cand, Lc, ncand, of, mq);
+                k_rq8_cand<RTV, B, PQV><<<gw, 256, lq, s>>>(
+                    idx->rq_codes, idx->cap, idx->rq_meta, PQV ? own : valid, idx->hiwater, qsrc, c0, a.qmeta, D, fl2, fcos,
+                    cand, Lc, ncand, (int)cn, R, idx->id_base, idx->ascI.as<uint64_t>() + c0 * R,
+                    idx->ascD.as<float>() + c0 * R, idx->ascN.as<int32_t>() + c0, of, own_vq, mq);
+            };
+            for_rt(RT, [&](auto rt) {
+                auto with_bits = [&](auto pq) {
+                    if (bits == 8) run(rt, std::integral_constant<int, 8>{}, pq);
+                    else run(rt, std::integral_constant<int, 1>{}, pq);
+                };
+                if (own) with_bits(std::true_type{});
+                else with_bits(std::false_type{});
+            });
+        });
+    if (rc) return rc;
     idx->stats.mfma_launches++;
     idx->stats.last_route = WV_ROUTE_RQ8_INT8;
     return WV_OK;

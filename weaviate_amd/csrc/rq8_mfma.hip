@@ -14,7 +14,9 @@
 //   k_rq8_keys  the exact rq-8 distance of every (query, row) of a 32-row
 //               block, reduced in registers to the block minimum (a NaN
 //               distance -> -inf: its block is always a candidate and the
-//               query is replayed)
+//               query is replayed).  i8_ring_keys<NC, Codec> below is the
+//               same ring with the side pieces, query state and epilogue
+//               left to a codec: k_sq_keys' body (sq_mfma.hip)
 //               (k_rq8_keys_cp: the same keys for 1024 < D <= 4096, the block
 //               streamed in column parts; instantiated in rq8_wide.hip)
 //   k_rq8_sel   wave per query: M = the (R+1)-th smallest block minimum;
@@ -112,10 +114,13 @@ __device__ __forceinline__ uint32_t rq8_lds_ld4(unsigned addr) {
     return v;
 }
 
-// ring slots of k_rq8_keys: as many as 150 KiB of LDS holds, 4..8
+// ring slot of k_rq8_keys: a block's codes, then its meta (512 B), code sums (128 B) and valid word
+__host__ __device__ constexpr int rq8_slot(int NC) { return 32 * 64 * NC + 656; }
+// ring slots of i8_ring_keys: as many rq-8 slots as 150 KiB of LDS holds, 4..8
+// (k_sq_keys' slot is smaller; it runs at the same depth)
 __host__ __device__ constexpr int rq8_nbuf(int NC) {
-    return (150 * 1024) / (32 * 64 * NC + 656) > 8 ? 8 : (150 * 1024) / (32 * 64 * NC + 656) < 4 ? 4
-                                                                                              : (150 * 1024) / (32 * 64 * NC + 656);
+    const int n = (150 * 1024) / rq8_slot(NC);
+    return n > 8 ? 8 : n < 4 ? 4 : n;
 }
 
 // ---------------------------------------------------------------------------
@@ -316,6 +321,12 @@ __device__ __forceinline__ void rq8_block_min(const i32x4_t (&acc)[2][NQ], unsig
 // the next chunk's issued before this chunk's MFMAs), 4 MFMAs.  acc[m][n][r]
 // is row 16m + 4g + r (g = lane >> 4) of query 16n + (lane & 15); the C input
 // of the first chunk is 128 Sy, the epilogue adds 128 Sx - 16384 D.
+//   This is i8_ring_keys (below, k_sq_keys' body) written out for rq's side
+// pieces and epilogue, and a change to the ring has to be made in both.  Routed
+// through that body the rq kernels compile to other code (the packed fp32
+// operations of rq8_block_min's fast forms get their operands in the other
+// order), which a refactor of it has to show to be as fast; until then the
+// kernel stays as it was, bit for bit.
 // ---------------------------------------------------------------------------
 template <int NC, int BITS>
 __global__ __launch_bounds__(512, 2) void k_rq8_keys(RQ8Args a) {
@@ -325,7 +336,7 @@ __global__ __launch_bounds__(512, 2) void k_rq8_keys(RQ8Args a) {
     constexpr int MB = CB;              // meta: 32 x 16 B
     constexpr int SB = CB + 512;        // code sums: 32 x 4 B
     constexpr int VB = CB + 640;        // valid word
-    constexpr int SLOT = CB + 656;
+    constexpr int SLOT = rq8_slot(NC);
     constexpr int NP = 2 * NC + 3;      // wave-wide loads per block
     constexpr int PW = (NP + 7) / 8;    // per wave (padded: every wave issues PW)
     // a late wave reads block t-1's meta while block t + AHEAD lands
@@ -483,6 +494,186 @@ __global__ __launch_bounds__(512, 2) void k_rq8_keys(RQ8Args a) {
     }
     if (!late && nsteps > 0 && lane < 32) krow[b0 + nsteps - 1] = pend;
 }
+
+// ---------------------------------------------------------------------------
+// i8_ring_keys<NC, Codec>: k_rq8_keys' ring with the codec-specific parts left
+// to a policy; the body of k_sq_keys (sq_mfma.hip), not yet of k_rq8_keys (above):
+// block minima of 256 queries (8 waves x 32, their int8 codes in VGPRs as B
+// fragments) x one span of 32-row blocks, padded width D = 64 NC.  A block's
+// codes (32 D bytes: 2 NC 1-KiB pieces, [16-byte chunk][row]) and the codec's
+// side pieces behind them (per-row sums or meta, the valid word) land in an
+// LDS ring of rq8_nbuf(NC) slots (at LDS address `ring`) by LDS-DMA, NBUF - 2
+// blocks ahead; one barrier per block.  Per 64-column chunk: 2 A-fragment
+// reads (row halves, the next chunk's issued before this chunk's MFMAs), 4
+// MFMAs.  acc[m][n][r] is row 16m + 4g + r (g = lane >> 4) of query 16n +
+// (lane & 15); the C input of the first chunk comes from the codec (128 Sy:
+// the epilogue adds 128 Sx - 16384 d).  The Codec (SQ8Codec) has:
+//   Args                 the kernel's operands; Qp, key, ldk, nblk,
+//                        blocks_per_span, nspans, nqg are read here
+//   slot_bytes(NC), SIDE a slot's size; the wave-wide loads behind the codes
+//   codes(a)             the signed code plane (rq_tile_u4)
+//   side(a, blk, k, lane, tail)  issues side piece k of block blk to `tail`,
+//                        the slot's bytes behind the codes
+//   QMeta, load_query    ym[n], C0[n]: the per-query state and first C input
+//                        of query q0 + 16n + j; returns qfine (rq: both norms
+//                        admit the fast epilogue; SQ: unused)
+//   epilogue             acc, the slot's tail, ym and qfine -> out[n], the
+//                        block minimum of query 16n + (lane & 15)
+//   dbg(a)               option rq_serial's bits 1 (no lookahead), 2 (no
+//                        stagger), 16 (no MFMAs); a constant 0 folds them away
+// ---------------------------------------------------------------------------
+template <int NC, class Codec>
+__device__ __forceinline__ void i8_ring_keys(const typename Codec::Args& a, const unsigned ring) {
+    constexpr int D = 64 * NC;
+    constexpr int CB = 32 * D;          // code bytes per block; the side pieces follow
+    constexpr int SLOT = Codec::slot_bytes(NC);
+    constexpr int NP = 2 * NC + Codec::SIDE;  // wave-wide loads per block
+    constexpr int PW = (NP + 7) / 8;    // per wave (padded: every wave issues PW)
+    // a late wave reads block t-1's side pieces while block t + AHEAD lands
+    constexpr int NBUF = rq8_nbuf(NC);
+    constexpr int AHEAD = NBUF - 2;
+    static_assert(SLOT % 16 == 0, "slot alignment");
+    static_assert(NBUF * SLOT <= 160 * 1024, "LDS");
+    static_assert((NC - 1) * 2048 + 256 < 65536, "ds_read offsets");
+
+    const int dbg = Codec::dbg(a);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int total = a.nqg * a.nspans;
+    const int b = blockIdx.x;
+    // XCD-aware order: the query groups of one span share an XCD (its L2)
+    const int logical = (total % 8 == 0) ? (b % 8) * (total / 8) + (b / 8) : b;
+    const int span = logical / a.nqg, grp = logical % a.nqg;
+    const int j = lane & 15, g = lane >> 4;
+    const int64_t q0 = (int64_t)grp * 256 + wave * 32;
+
+    // Qf[2c + n]: query q0 + 16n + j, columns 64c + 16g .. +15
+    i32x4_t Qf[2 * NC];
+    {
+        const unsigned char* qp = a.Qp + (q0 + j) * D + 16 * g;
+#pragma unroll
+        for (int c = 0; c < NC; c++)
+#pragma unroll
+            for (int n = 0; n < 2; n++)
+                Qf[2 * c + n] = *reinterpret_cast<const i32x4_t*>(qp + (int64_t)n * 16 * D + 64 * c);
+    }
+    typename Codec::QMeta ym[2];
+    i32x4_t C0[2];
+    const bool qfine = Codec::load_query(a, q0, j, ym, C0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the query loads retire before the DMA ring
+
+    const int64_t b0 = (int64_t)span * a.blocks_per_span;
+    int64_t b1 = b0 + a.blocks_per_span;
+    if (b1 > a.nblk) b1 = a.nblk;
+    const int nsteps = b1 > b0 ? (int)(b1 - b0) : 0;
+    auto issue = [&](int t, int slot) {
+        const int64_t blk = b0 + t;
+        const unsigned char* gb = Codec::codes(a) + blk * CB;  // the block's contiguous run (rq_tile_u4)
+        const unsigned sb = ring + (unsigned)(slot * SLOT);
+        static_for<0, PW>([&](auto jc) {
+            constexpr int jj = decltype(jc)::value;
+            int p = wave + 8 * jj;
+            if (p >= NP) p -= NP;  // padding: a copy of a piece another wave loads (same bytes, same place)
+            if (p < 2 * NC) {
+                __builtin_amdgcn_global_load_lds(gb + p * 1024 + 16 * lane, (lds_ptr_t)(size_t)(sb + (unsigned)(p * 1024)),
+                                                 16, 0, 0);
+            } else {
+                Codec::side(a, blk, p - 2 * NC, lane, sb + CB);
+            }
+        });
+    };
+    const int ahead = (dbg & 1) ? 1 : AHEAD;
+    for (int t = 0; t < ahead && t < nsteps; t++) issue(t, t);
+
+    const unsigned l16 = (unsigned)(g * 512 + j * 16);
+    float* krow = a.key + (q0 + (lane & 31)) * a.ldk;
+    // Waves 4-7 (each the SIMD partner of wave w - 4) run block t-1's
+    // epilogue before block t's MFMAs instead of after them, so the two
+    // waves of a SIMD alternate MFMA and VALU phases (MI355X_MICROARCH.md, two
+    // waves per SIMD: a stagger) instead of issuing both at once.
+    const bool late = wave >= 4 && !(dbg & 2);
+    i32x4_t acc[2][2];
+    float pend = 0.f;  // an early wave's key of the previous block, stored after the next barrier
+    auto mfma_block = [&](unsigned sb) {
+        const unsigned ab = sb + l16;
+        i32x4_t A[2][2];
+        A[0][0] = lds_ld16_o<0>(ab);
+        A[0][1] = lds_ld16_o<256>(ab);
+        static_for<0, NC>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            if constexpr (c + 1 < NC) {
+                A[(c + 1) & 1][0] = lds_ld16_o<(c + 1) * 2048>(ab);
+                A[(c + 1) & 1][1] = lds_ld16_o<(c + 1) * 2048 + 256>(ab);
+                qs_wait_lgkm<2>();
+            } else {
+                qs_wait_lgkm<0>();
+            }
+            asm volatile("" : "+v"(A[c & 1][0]), "+v"(A[c & 1][1]));
+            __builtin_amdgcn_sched_barrier(0);
+            if (dbg & 16) {  // timing experiment: no MFMAs (wrong keys)
+                acc[0][0] = A[c & 1][0];
+                acc[1][1] = A[c & 1][1];
+                return;
+            }
+#pragma unroll
+            for (int m = 0; m < 2; m++)
+#pragma unroll
+                for (int n = 0; n < 2; n++)
+                    acc[m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[c & 1][m], Qf[2 * c + n],
+                                                                      c == 0 ? C0[n] : acc[m][n], 0, 0, 0);
+        });
+    };
+    // a block's epilogue (its side pieces in slot sb, its sums in acc) -> the
+    // lane's key of it (lanes 0-15: queries j, lanes 16-31: queries 16 + j)
+    auto epilogue = [&](unsigned sb) -> float {
+        float m[2];
+        Codec::epilogue(acc, sb + CB, ym, qfine, a, D, lane, m);
+        return (lane & 16) ? m[1] : m[0];
+    };
+    for (int t = 0; t <= nsteps; t++) {
+        const int cur = t % NBUF;
+        if (t < nsteps) {
+            // block t's pieces landed: vector-memory ops retire in issue order
+            // (loads, stores and LDS-DMA alike), so the wait leaves in flight
+            // exactly the ops issued after them: the pieces of the blocks up to
+            // t + ahead - 1 and the key stores of the steps since (an early
+            // wave stores before its step's pieces, a late wave after them).
+            // Counting the stores keeps the scattered key writes out of the
+            // critical path.
+            const int later = nsteps - 1 - t < ahead - 1 ? nsteps - 1 - t : ahead - 1;  // blocks issued after t
+            const int fs = t < ahead ? 1 : (late ? (t - ahead > 1 ? t - ahead : 1) : (t - ahead + 1 > 1 ? t - ahead + 1 : 1));
+            const int nst = t > fs ? t - fs : 0;  // the stores of steps fs .. t-1
+            qs_wait_vm(PW * later + nst);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            if (!late && t > 0 && lane < 32) krow[b0 + t - 1] = pend;
+            if (t + ahead < nsteps) issue(t + ahead, (t + ahead) % NBUF);
+        }
+        if (!late) {
+            if (t < nsteps) {
+                mfma_block(ring + (unsigned)(cur * SLOT));
+                pend = epilogue(ring + (unsigned)(cur * SLOT));
+            }
+        } else {
+            if (t > 0) {
+                const float kv = epilogue(ring + (unsigned)(((t - 1) % NBUF) * SLOT));
+                if (lane < 32) krow[b0 + t - 1] = kv;
+            }
+            if (t < nsteps) mfma_block(ring + (unsigned)(cur * SLOT));
+        }
+    }
+    if (!late && nsteps > 0 && lane < 32) krow[b0 + nsteps - 1] = pend;
+}
+
+// what launch_ring_keys needs of the rq kernels: their operands, slot and entry
+template <int BITS>
+struct RQ8Codec {
+    typedef RQ8Args Args;
+    static constexpr int slot_bytes(int NC) { return rq8_slot(NC); }
+    template <int NC>
+    static auto kernel() { return &k_rq8_keys<NC, BITS>; }
+};
 
 // ---------------------------------------------------------------------------
 // k_rq8_keys_cp<NP, BITS>: k_rq8_keys for 1024 < D <= 4096 (NC = a.nc = D / 64

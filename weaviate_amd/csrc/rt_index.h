@@ -125,6 +125,36 @@ static inline void for_metric_variant(int metric, int variant, F&& f) {
     else if (metric == WV_METRIC_MANHATTAN) f(std::integral_constant<int, MANHATTAN>{}, std::integral_constant<int, AVX256>{});
     else f(std::integral_constant<int, HAMMING>{}, std::integral_constant<int, AVX256>{});
 }
+// f(std::integral_constant<int, NC>) for the 64-column chunk count of k_rq8_keys / k_sq_keys, 1..16
+template <int N = 1, class F>
+static inline void for_ring_nc(int NC, F&& f) {
+    if constexpr (N < 16) {
+        if (NC == N) f(std::integral_constant<int, N>{});
+        else for_ring_nc<N + 1>(NC, f);
+    } else {
+        f(std::integral_constant<int, 16>{});
+    }
+}
+// f(std::integral_constant<int, RT>) for a WaveTopL list of 64 (RT - 1) entries: qs_R's 2, 4, 8, 16
+template <class F>
+static inline void for_rt(int RT, F&& f) {
+    if (RT == 2) f(std::integral_constant<int, 2>{});
+    else if (RT == 4) f(std::integral_constant<int, 4>{});
+    else if (RT == 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
+}
+// k_rq8_keys / k_sq_keys (Codec: RQ8Codec<BITS> / SQ8Codec<METRIC>) for NC chunks over the ring i8_ring_keys
+// lays out.  A refused LDS limit is not checked here: the launch then fails, and the caller reads that error.
+template <class Codec>
+static inline void launch_ring_keys(const typename Codec::Args& a, int NC, unsigned grid, hipStream_t s) {
+    for_ring_nc(NC, [&](auto nc) {
+        constexpr int N = decltype(nc)::value;
+        constexpr size_t lds = (size_t)rq8_nbuf(N) * Codec::slot_bytes(N);
+        const auto k = Codec::template kernel<N>();
+        (void)set_dyn_lds((const void*)k, lds);
+        k<<<grid, 512, lds, s>>>(a);
+    });
+}
 
 struct wv_batcher;
 static void batcher_free(wv_index* idx, wv_batcher* b);
@@ -327,7 +357,7 @@ struct wv_index {
     DBuf pq8Max, pq8Mu, pq8Tmp, pq8Qc, qsCand2;
     DBuf rq8Qp, rq8Qcs, rq8Qm, rq8Fq, rq8Fm;                  // rq-8 MFMA route: query planes, flagged queries
     DBuf rq8M;                                                // a multi-allow batch: the select's threshold M per query
-    int rq_mfma = 1;
+    int rq_mfma = 1;        // option rq_mfma: rq-8 / rq-1 on the integer matrix cores
     int rq_wide = -1;       // option rq_wide: 1024 < D <= 4096 on the matrix cores too (k_rq8_keys_cp): 1, never (0), auto (-1)
     // per-query allow lists (wv_index_search_by_vector_batch_multi_allow):
     // pqa_cur is the shared launch in flight, set by pqa_run for the length of
@@ -349,7 +379,7 @@ struct wv_index {
     bool cur_pqk = false;   // search_qs: this batch's keys are per-query (the replays' upper bounds hold)
     DBuf pqaBits, pqaUnion, pqaIds, pqaQ, pqaM, pqaM2, qsT;
     int64_t q8_bm_min = 64;                                   // option q8_bm_min: smallest batch for the block-major int8 filter
-    int rq_serial = 0;                                        // option rq_serial (debug): k_rq8_keys without the DMA lookahead                                          // option rq_mfma: rq-8 on the integer matrix cores
+    int rq_serial = 0;                                        // option rq_serial (debug): k_rq8_keys without the DMA lookahead
     DBuf pqZero;                                              // zero norms / qinfo for k_blk_select over ADC minima
     DBuf flCtr;                      // device flag-list counters (replay_flags)
     int64_t qs_phase_nq = 0;         // sharded phase 1 done for this batch size
@@ -391,6 +421,31 @@ static inline void sq8_mark(wv_index* idx, int64_t lo, int64_t hi) {
 static inline int64_t rq8_chunk(const wv_index* idx) {
     const int64_t nblk = (idx->hiwater + 31) / 32;
     return std::max<int64_t>(256, ((4ll << 30) / (nblk * 4)) / 256 * 256);
+}
+// their loop over chunks of QC queries (a: RQ8Args / SQ8Args, QG queries per workgroup): the chunk's spans
+// (ring_span_plan) into a, then keys(c0, grid) -- the chunk's query operands into a and the key kernel, timed
+// for the first chunk -- and cands(c0, cn, gw, cand, ncand, oflag): the select and candidate kernels, wave per
+// query (gw workgroups), over the chunk's rows of qsCand (Lc entries per query) / qsNc / oF
+template <class Args, class Keys, class Cands>
+static inline int ring_query_chunks(wv_index* idx, hipStream_t s, int64_t nq, int64_t QC, int QG, int Lc, Args& a,
+                                    Keys&& keys, Cands&& cands) {
+    for (int64_t c0 = 0; c0 < nq; c0 += QC) {
+        const int64_t cn = std::min<int64_t>(QC, nq - c0);
+        a.nqg = (int)(round_up(cn, 256) / QG);
+        const RingSpanPlan plan = ring_span_plan(a.nqg, a.nblk);
+        a.blocks_per_span = plan.blocks_per_span;
+        a.nspans = plan.nspans;
+        const bool time_it = idx->timing && c0 == 0;
+        if (time_it) HIPCHK(hipEventRecord(idx->ev0, s));
+        const int rc = keys(c0, (unsigned)(a.nqg * plan.nspans));
+        if (rc) return rc;
+        HIPCHK(hipGetLastError());
+        if (time_it) HIPCHK(hipEventRecord(idx->ev1, s));
+        cands(c0, cn, (unsigned)((cn + 3) / 4), idx->qsCand.as<uint32_t>() + c0 * Lc, idx->qsNc.as<int32_t>() + c0,
+              idx->oF.as<int32_t>() + c0);
+        HIPCHK(hipGetLastError());
+    }
+    return WV_OK;
 }
 static void invalidate_batch(wv_index* idx) {
     idx->qs_keys_nq = 0;

@@ -13,7 +13,9 @@
 // constant uses d, not the padded width.
 //   k_sq_plane  the signed plane of a dirty slot range, 32-row tiles (rq_tile_u4)
 //   k_sq_qprep  the encoded queries (sqq / sqm) -> signed rows, padded to 256
-//   k_sq_keys   exact 32-row block minima of k_sq_dist's distance
+//   k_sq_keys   exact 32-row block minima of k_sq_dist's distance: k_rq8_keys'
+//               ring as a body with a codec (i8_ring_keys, rq8_mfma.hip) and
+//               SQ's side pieces and epilogue (SQ8Codec)
 //   k_rq8_sel   (rq8_mfma.hip) M = the (R+1)-th smallest minimum, candidates
 //   k_sq_cand   exact distances of the candidates' rows from the u8 codes as
 //               k_sq_dist computes them; the R+1 smallest strictly increasing
@@ -164,164 +166,53 @@ __device__ __forceinline__ void sq_block_key(const i32x4_t (&acc)[2][2], unsigne
     }
 }
 
-// ring slot of k_sq_keys: the block's signed codes, {Sx, sum2_x} and valid word
-__host__ __device__ constexpr int sq8_slot(int NC) { return 32 * 64 * NC + 272; }
+template <int NC, int METRIC>
+__global__ void k_sq_keys(SQ8Args a);
 
-// ---------------------------------------------------------------------------
-// k_sq_keys<NC, METRIC>: block minima of 256 queries (8 waves x 32, their
-// signed codes in VGPRs as B fragments) x one span of 32-row blocks, padded
-// width 64 NC.  The work split is k_rq8_keys': a block's codes (2 NC 1-KiB
-// pieces, [16-byte chunk][row]), its 32 {Sx, sum2_x} (256 B) and its valid word
-// land in an LDS ring of rq8_nbuf(NC) slots by LDS-DMA, NBUF - 2 blocks ahead;
-// one barrier per block; per 64-column chunk 2 A-fragment reads (row halves,
-// the next chunk's issued before this chunk's MFMAs) and 4 MFMAs.  The C input
-// of the first chunk is 128 Sy; the epilogue adds 128 Sx - 16384 d.  Waves 4-7
-// run block t-1's epilogue before block t's MFMAs, so the two waves of a SIMD
-// alternate matrix and VALU phases.  Counted waits: a wave's vector-memory ops
-// retire in issue order, so vmcnt leaves in flight exactly the pieces of the
-// blocks issued after the awaited one and the key stores since.
-// ---------------------------------------------------------------------------
+// SQ in i8_ring_keys (rq8_mfma.hip): behind a block's signed codes its 32
+// {Sx, sum2_x} (256 B) and its valid word; the C input of the first chunk is
+// 128 Sy, the epilogue (sq_block_key) adds 128 Sx - 16384 d; no debug bits
+template <int METRIC>
+struct SQ8Codec {
+    static_assert(METRIC == L2 || METRIC == DOT, "l2-squared, or dot / cosine");
+    typedef SQ8Args Args;
+    template <int NC>
+    static auto kernel() { return &k_sq_keys<NC, METRIC>; }  // (launch_ring_keys)
+    static constexpr int SIDE = 2, META = 0, VALID = 256;
+    static constexpr int slot_bytes(int NC) { return 32 * 64 * NC + VALID + 16; }
+    typedef uint2 QMeta;
+    static __device__ __forceinline__ const unsigned char* codes(const Args& a) { return a.plane; }
+    static __device__ __forceinline__ int dbg(const Args&) { return 0; }
+    static __device__ __forceinline__ void side(const Args& a, int64_t blk, int k, int lane, unsigned tail) {
+        if (k == 0) {
+            if (lane < 16)
+                __builtin_amdgcn_global_load_lds(a.meta + blk * 32 + 2 * lane, (lds_ptr_t)(size_t)(tail + META), 16, 0, 0);
+        } else {
+            if (lane == 0) __builtin_amdgcn_global_load_lds(a.valid + blk, (lds_ptr_t)(size_t)(tail + VALID), 4, 0, 0);
+        }
+    }
+    static __device__ __forceinline__ bool load_query(const Args& a, int64_t q0, int j, uint2 (&ym)[2],
+                                                      i32x4_t (&C0)[2]) {
+#pragma unroll
+        for (int n = 0; n < 2; n++) {
+            ym[n] = a.Qs[q0 + 16 * n + j];
+            const int ky = (int)(128u * ym[n].x);
+            C0[n] = i32x4_t{ky, ky, ky, ky};
+        }
+        return true;
+    }
+    static __device__ __forceinline__ void epilogue(const i32x4_t (&acc)[2][2], unsigned tail, const uint2 (&ym)[2], bool,
+                                                    const Args& a, int, int lane, float (&out)[2]) {
+        sq_block_key<METRIC>(acc, tail + META, tail + VALID, ym, a, lane, out);
+    }
+};
+
+// k_sq_keys<NC, METRIC>: i8_ring_keys over the signed SQ plane, padded width
+// 64 NC, at the ring depth sized for rq-8's larger slot (rq8_nbuf)
 template <int NC, int METRIC>
 __global__ __launch_bounds__(512, 2) void k_sq_keys(SQ8Args a) {
-    constexpr int DP = 64 * NC;
-    constexpr int CB = 32 * DP;         // code bytes per block
-    constexpr int MB = CB;              // {Sx, sum2_x}: 32 x 8 B
-    constexpr int VB = CB + 256;        // valid word
-    constexpr int SLOT = sq8_slot(NC);
-    constexpr int NP = 2 * NC + 2;      // wave-wide loads per block
-    constexpr int PW = (NP + 7) / 8;    // per wave (padded: every wave issues PW)
-    constexpr int NBUF = rq8_nbuf(NC);  // (sized for rq-8's larger slot)
-    constexpr int AHEAD = NBUF - 2;     // a late wave reads block t-1's sums while block t + AHEAD lands
-    static_assert(METRIC == L2 || METRIC == DOT, "l2-squared, or dot / cosine");
-    static_assert(SLOT % 16 == 0, "slot alignment");
-    static_assert(NBUF * SLOT <= 160 * 1024, "LDS");
-    static_assert((NC - 1) * 2048 + 256 < 65536, "ds_read offsets");
     extern __shared__ __attribute__((aligned(16))) unsigned char ssm[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int total = a.nqg * a.nspans;
-    const int b = blockIdx.x;
-    // XCD-aware order: the query groups of one span share an XCD (its L2)
-    const int logical = (total % 8 == 0) ? (b % 8) * (total / 8) + (b / 8) : b;
-    const int span = logical / a.nqg, grp = logical % a.nqg;
-    const int j = lane & 15, g = lane >> 4;
-    const int64_t q0 = (int64_t)grp * 256 + wave * 32;
-
-    // Qf[2c + n]: query q0 + 16n + j, columns 64c + 16g .. +15
-    i32x4_t Qf[2 * NC];
-    {
-        const unsigned char* qp = a.Qp + (q0 + j) * DP + 16 * g;
-#pragma unroll
-        for (int c = 0; c < NC; c++)
-#pragma unroll
-            for (int n = 0; n < 2; n++)
-                Qf[2 * c + n] = *reinterpret_cast<const i32x4_t*>(qp + (int64_t)n * 16 * DP + 64 * c);
-    }
-    uint2 ym[2];
-    i32x4_t C0[2];
-#pragma unroll
-    for (int n = 0; n < 2; n++) {
-        ym[n] = a.Qs[q0 + 16 * n + j];
-        const int ky = (int)(128u * ym[n].x);
-        C0[n] = i32x4_t{ky, ky, ky, ky};
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the query loads retire before the DMA ring
-
-    const int64_t b0 = (int64_t)span * a.blocks_per_span;
-    int64_t b1 = b0 + a.blocks_per_span;
-    if (b1 > a.nblk) b1 = a.nblk;
-    const int nsteps = b1 > b0 ? (int)(b1 - b0) : 0;
-    const unsigned ring = lds_addr(ssm);
-    auto issue = [&](int t, int slot) {
-        const int64_t blk = b0 + t;
-        const unsigned char* gb = a.plane + blk * CB;  // the block's contiguous run (rq_tile_u4)
-        const unsigned sb = ring + (unsigned)(slot * SLOT);
-        static_for<0, PW>([&](auto jc) {
-            constexpr int jj = decltype(jc)::value;
-            int p = wave + 8 * jj;
-            if (p >= NP) p -= NP;  // padding: a copy of a piece another wave loads (same bytes, same place)
-            if (p < 2 * NC) {
-                __builtin_amdgcn_global_load_lds(gb + p * 1024 + 16 * lane, (lds_ptr_t)(size_t)(sb + (unsigned)(p * 1024)),
-                                                 16, 0, 0);
-            } else if (p == 2 * NC) {
-                if (lane < 16)
-                    __builtin_amdgcn_global_load_lds(a.meta + blk * 32 + 2 * lane, (lds_ptr_t)(size_t)(sb + MB), 16, 0, 0);
-            } else {
-                if (lane == 0)
-                    __builtin_amdgcn_global_load_lds(a.valid + blk, (lds_ptr_t)(size_t)(sb + VB), 4, 0, 0);
-            }
-        });
-    };
-    for (int t = 0; t < AHEAD && t < nsteps; t++) issue(t, t);
-
-    const unsigned l16 = (unsigned)(g * 512 + j * 16);
-    float* krow = a.key + (q0 + (lane & 31)) * a.ldk;
-    const bool late = wave >= 4;
-    i32x4_t acc[2][2];
-    float pend = 0.f;  // an early wave's key of the previous block, stored after the next barrier
-    auto mfma_block = [&](unsigned sb) {
-        const unsigned ab = sb + l16;
-        i32x4_t A[2][2];
-        A[0][0] = lds_ld16_o<0>(ab);
-        A[0][1] = lds_ld16_o<256>(ab);
-        static_for<0, NC>([&](auto cc) {
-            constexpr int c = decltype(cc)::value;
-            if constexpr (c + 1 < NC) {
-                A[(c + 1) & 1][0] = lds_ld16_o<(c + 1) * 2048>(ab);
-                A[(c + 1) & 1][1] = lds_ld16_o<(c + 1) * 2048 + 256>(ab);
-                qs_wait_lgkm<2>();
-            } else {
-                qs_wait_lgkm<0>();
-            }
-            asm volatile("" : "+v"(A[c & 1][0]), "+v"(A[c & 1][1]));
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int m = 0; m < 2; m++)
-#pragma unroll
-                for (int n = 0; n < 2; n++)
-                    acc[m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[c & 1][m], Qf[2 * c + n],
-                                                                      c == 0 ? C0[n] : acc[m][n], 0, 0, 0);
-        });
-    };
-    // a block's epilogue (its sums in slot sb, its products in acc) -> the lane's
-    // key of it (lanes 0-15: queries j, lanes 16-31: queries 16 + j)
-    auto epilogue = [&](unsigned sb) -> float {
-        float m[2];
-        sq_block_key<METRIC>(acc, sb + MB, sb + VB, ym, a, lane, m);
-        return (lane & 16) ? m[1] : m[0];
-    };
-    for (int t = 0; t <= nsteps; t++) {
-        const int cur = t % NBUF;
-        if (t < nsteps) {
-            // block t's pieces landed: in flight stay the pieces of the blocks up
-            // to t + AHEAD - 1 and the key stores of the steps since block t's
-            // issue (an early wave stores before its step's pieces, a late wave
-            // after them)
-            const int later = nsteps - 1 - t < AHEAD - 1 ? nsteps - 1 - t : AHEAD - 1;  // blocks issued after t
-            const int fs = t < AHEAD ? 1 : (late ? (t - AHEAD > 1 ? t - AHEAD : 1) : (t - AHEAD + 1 > 1 ? t - AHEAD + 1 : 1));
-            const int nst = t > fs ? t - fs : 0;  // the stores of steps fs .. t-1
-            qs_wait_vm(PW * later + nst);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            if (!late && t > 0 && lane < 32) krow[b0 + t - 1] = pend;
-            if (t + AHEAD < nsteps) issue(t + AHEAD, (t + AHEAD) % NBUF);
-        }
-        if (!late) {
-            if (t < nsteps) {
-                mfma_block(ring + (unsigned)(cur * SLOT));
-                pend = epilogue(ring + (unsigned)(cur * SLOT));
-            }
-        } else {
-            if (t > 0) {
-                const float kv = epilogue(ring + (unsigned)(((t - 1) % NBUF) * SLOT));
-                if (lane < 32) krow[b0 + t - 1] = kv;
-            }
-            if (t < nsteps) mfma_block(ring + (unsigned)(cur * SLOT));
-        }
-    }
-    if (!late && nsteps > 0 && lane < 32) krow[b0 + nsteps - 1] = pend;
+    i8_ring_keys<NC, SQ8Codec<METRIC>>(a, lds_addr(ssm));
 }
 
 // the SQ distance of stored row `slot` to one query as k_sq_dist computes it:
@@ -448,19 +339,6 @@ __global__ void k_sq_gather_q(const uint4* __restrict__ qcodes, const uint2* __r
     if (c == 0) ometa[f] = qmeta[q];
 }
 
-template <int NC>
-void launch_sq_keys(const SQ8Args& a, unsigned grid, hipStream_t s, bool l2) {
-    constexpr size_t lds = (size_t)rq8_nbuf(NC) * sq8_slot(NC);  // the ring
-    // a refused limit is not checked here: the launch then fails, and the caller reads that error
-    if (l2) {
-        (void)set_dyn_lds((const void*)k_sq_keys<NC, L2>, lds);
-        k_sq_keys<NC, L2><<<grid, 512, lds, s>>>(a);
-    } else {
-        (void)set_dyn_lds((const void*)k_sq_keys<NC, DOT>, lds);
-        k_sq_keys<NC, DOT><<<grid, 512, lds, s>>>(a);
-    }
-}
-
 }  // namespace
 
 // option sq_keys = -1: the batch sizes and corpus sizes where the route won the
@@ -552,60 +430,26 @@ int sq8_candidates(wv_index* idx, hipStream_t s, int64_t nq, int R, const uint32
     a.a2 = idx->sq_a2;
     a.ab = idx->sq_ab;
     a.ib2 = idx->sq_ib2;
-    for (int64_t c0 = 0; c0 < nq; c0 += QC) {
-        const int64_t cn = std::min<int64_t>(QC, nq - c0);
-        a.Qp = Qp + c0 * DP;
-        a.Qs = Qs + c0;
-        a.nqg = (int)(round_up(cn, 256) / 256);
-        // spans: ~2048 workgroups (8 per CU), at least 16 blocks each
-        int64_t nspans = std::max<int64_t>(1, std::min<int64_t>(nblk / 16, (2048 + a.nqg - 1) / a.nqg));
-        const int64_t bps = (nblk + nspans - 1) / nspans;
-        nspans = (nblk + bps - 1) / bps;
-        a.blocks_per_span = (int)bps;
-        a.nspans = (int)nspans;
-        const unsigned grid = (unsigned)(a.nqg * nspans);
-        const bool time_it = idx->timing && c0 == 0;
-        if (time_it) HIPCHK(hipEventRecord(idx->ev0, s));
-        const bool l2 = metric == L2;
-        switch (NC) {
-        case 1: launch_sq_keys<1>(a, grid, s, l2); break;
-        case 2: launch_sq_keys<2>(a, grid, s, l2); break;
-        case 3: launch_sq_keys<3>(a, grid, s, l2); break;
-        case 4: launch_sq_keys<4>(a, grid, s, l2); break;
-        case 5: launch_sq_keys<5>(a, grid, s, l2); break;
-        case 6: launch_sq_keys<6>(a, grid, s, l2); break;
-        case 7: launch_sq_keys<7>(a, grid, s, l2); break;
-        case 8: launch_sq_keys<8>(a, grid, s, l2); break;
-        case 9: launch_sq_keys<9>(a, grid, s, l2); break;
-        case 10: launch_sq_keys<10>(a, grid, s, l2); break;
-        case 11: launch_sq_keys<11>(a, grid, s, l2); break;
-        case 12: launch_sq_keys<12>(a, grid, s, l2); break;
-        case 13: launch_sq_keys<13>(a, grid, s, l2); break;
-        case 14: launch_sq_keys<14>(a, grid, s, l2); break;
-        case 15: launch_sq_keys<15>(a, grid, s, l2); break;
-        default: launch_sq_keys<16>(a, grid, s, l2); break;
-        }
-        HIPCHK(hipGetLastError());
-        if (time_it) HIPCHK(hipEventRecord(idx->ev1, s));
-        const unsigned gw = (unsigned)((cn + 3) / 4);
-        uint32_t* cand = idx->qsCand.as<uint32_t>() + c0 * Lc;
-        int32_t* ncand = idx->qsNc.as<int32_t>() + c0;
-        int32_t* of = idx->oF.as<int32_t>() + c0;
-#define WV_SQC(RTV)                                                                                                   \
-    do {                                                                                                              \
-        k_rq8_sel<RTV><<<gw, 256, 0, s>>>(a.key, nblk, nblk, (int)cn, R, cand, Lc, ncand, of, nullptr);              \
-        k_sq_cand<RTV><<<gw, 256, (size_t)4 * idx->sq_Dq, s>>>(                                                       \
-            idx->sq_codes, idx->sq_meta, nchq, valid, idx->hiwater, idx->sqq.as<uint4>(), idx->sqm.as<uint2>(), c0,   \
-            metric, a.a2, a.ab, a.ib2, cand, Lc, ncand, (int)cn, R, idx->id_base, idx->ascI.as<uint64_t>() + c0 * R, \
-            idx->ascD.as<float>() + c0 * R, idx->ascN.as<int32_t>() + c0, of);                                       \
-    } while (0)
-        if (RT == 2) WV_SQC(2);
-        else if (RT == 4) WV_SQC(4);
-        else if (RT == 8) WV_SQC(8);
-        else WV_SQC(16);
-#undef WV_SQC
-        HIPCHK(hipGetLastError());
-    }
+    rc = ring_query_chunks(
+        idx, s, nq, QC, 256, Lc, a,
+        [&](int64_t c0, unsigned grid) {
+            a.Qp = Qp + c0 * DP;
+            a.Qs = Qs + c0;
+            if (metric == L2) launch_ring_keys<SQ8Codec<L2>>(a, NC, grid, s);
+            else launch_ring_keys<SQ8Codec<DOT>>(a, NC, grid, s);
+            return WV_OK;
+        },
+        [&](int64_t c0, int64_t cn, unsigned gw, uint32_t* cand, int32_t* ncand, int32_t* of) {
+            for_rt(RT, [&](auto rt) {
+                constexpr int RTV = decltype(rt)::value;
+                k_rq8_sel<RTV><<<gw, 256, 0, s>>>(a.key, nblk, nblk, (int)cn, R, cand, Lc, ncand, of, nullptr);
+                k_sq_cand<RTV><<<gw, 256, (size_t)4 * idx->sq_Dq, s>>>(
+                    idx->sq_codes, idx->sq_meta, nchq, valid, idx->hiwater, idx->sqq.as<uint4>(), idx->sqm.as<uint2>(), c0,
+                    metric, a.a2, a.ab, a.ib2, cand, Lc, ncand, (int)cn, R, idx->id_base,
+                    idx->ascI.as<uint64_t>() + c0 * R, idx->ascD.as<float>() + c0 * R, idx->ascN.as<int32_t>() + c0, of);
+            });
+        });
+    if (rc) return rc;
     idx->stats.last_group_queries = (uint64_t)nq;
     idx->stats.mfma_launches++;
     idx->stats.last_route = WV_ROUTE_SQ_INT8;
